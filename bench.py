@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                 # BASELINE configs[2]: 1024 x 10 kb per GPU, weak scaling
     python bench.py --config 5 --gpus N --steps K --warmup W      # BASELINE configs[4]: 10 000 x 50 kb in total, strong scaling
+    python bench.py --full ...                                    # the same headline plus every side measurement (minutes)
     N > 1: one process per GPU.  Either launched by  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or bare — `python bench.py --gpus N` without WORLD_SIZE
     re-executes itself under torch.distributed.run on 127.0.0.1 with a free port (launcher_argv()).
@@ -17,9 +18,15 @@ resident in HBM (torch tensors wrapped zero-copy by the C ABI), every pair's (s,
 (mwf_gpu_batch_results: one device-to-host copy, and any pair that needs a re-run gets it inside the step), and — at
 N > 1 — the one RCCL collective that gathers the records of all ranks.  `value` = bases aligned by all ranks / wall.
 The host-buffers-in to host-results-out rate of the same batch (PCIe both ways, warmed, pooled allocations) is
-printed beside it as `end_to_end_gbps`; it is never `value`.
+printed beside it as `end_to_end_gbps` (--full); it is never `value`.
 
-Printed JSON (one line, rank 0): the driver contract fields plus
+A plain run sets up, warms up, times --steps steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall milliseconds of one timed step, the workload under `config`).  --dump-outputs DIR also writes the records of
+the last timed step as DIR/<name>.npy (dump_outputs()); the inputs are seeded, so two builds can be compared output for output.
+Everything else the benchmark measures or checks takes runs of its own and needs --full:
+
+Printed JSON with --full (one line, rank 0): the fields above plus
+  gcells_per_s, seeds, kernel_gbps — from a kernel-only pass (HIP events) after the timed steps
   roofline     — ONE definition everywhere in the line (top level and long_pairs.*): achieved = HBM bytes per launch by the PMC
                  counters (profiles/traffic.json: 2048 B x FETCH_SIZE + 1024 B x WRITE_SIZE, units calibrated on this device) /
                  the kernel time measured live with HIP events on the launch stream; frac = achieved / 8 TB/s.  Named side fields:
@@ -27,7 +34,7 @@ Printed JSON (one line, rank 0): the driver contract fields plus
                  49 / 97 B per cell x cells / time — exceeds 1 for kernels that keep four of the five arrays on chip), issue fractions
   cpu_baseline — the compiled reference (oracle/_ref, kind "reference") or our C restatement (kind "port")
                  on the host cores, bounded sample of the same batch (rank 0, N=1 only)
-  call_latency_us, chain_mode, short_reads, long_pairs, peak_device_bytes, n_retries — extras (rank 0, N=1 only)
+  end_to_end, call_latency_us, chain_mode, short_reads, divergence_sweep, long_batches, long_pairs, peak_device_bytes — extras (rank 0, N=1 only)
 """
 from __future__ import annotations
 
@@ -572,7 +579,15 @@ def parse_args(argv=None):
     ap.add_argument("--mhc", nargs=2, metavar=("TARGET.fa", "QUERY.fa"), default=None, help="the reference's GRCh38 / CHM13 MHC pair instead of the synthetic 5 Mb stand-in: s must be 229868 (README.md:86)")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--seeds", type=int, default=4, help="batches of the headline shape rotated through the timed steps (config 3): value is the mean over them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (kernel-only timing and roofline, end_to_end, cpu_baseline, call latency, chain mode, "
+                         "short reads, divergence sweep, long batches, long pairs: minutes); without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (every pair's s and n_iter; with --cigar also n_cigar and the CIGAR words) "
+                         "as DIR/<name>.npy in float64")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.dry = os.environ.get("MWF_BENCH_BACKEND", "").lower() == "gloo"
     strong = args.config == 5
     if args.dry:     # the plumbing test: a few short pairs per rank
@@ -644,6 +659,8 @@ def dry_run(args, rank, world):
         for i in range(n_total):
             es, eit, _ = orc.align(*synth_pair(args.seed + i, args.tl, args.div), o)
             ok = ok and (int(s_all[i]), int(it_all[i])) == (es, eit)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, (s_all.numpy(), it_all.numpy(), None), None, None)
         print(json.dumps({
             "metric": "aligned Gbp/s (q+t)", "value": total_bases * args.steps / elapsed / 1e9, "unit": "Gbp/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
@@ -656,6 +673,31 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
     if not ok:
         raise SystemExit("dry run: gathered records differ from the oracle's")
+
+
+DUMP_BYTES_CAP = 64 << 20     # --dump-outputs writes at most this much
+
+
+def dump_outputs(path: str, last, cigar_batch, ids, gathered=None) -> list:
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float64 (every value is an integer that float64 holds
+    exactly).  `s` and `n_iter` of every pair (all ranks' at N > 1, from the step's gather); with CIGAR on also `n_cigar` of this rank's pairs
+    and their CIGAR words: `cigar` = the words of the pairs listed in `cigar_pairs` (global pair ids, ascending), concatenated in that
+    order — every pair, or a fixed seeded sample of them when every pair's words would pass DUMP_BYTES_CAP."""
+    s, it, nc = last
+    arrays = {"s": s, "n_iter": it} if gathered is None else {"s": gathered[0], "n_iter": gathered[1]}
+    if cigar_batch is not None:
+        arrays["n_cigar"] = nc
+        budget = DUMP_BYTES_CAP // 8 - 2 * len(arrays["s"]) - 2 * len(nc) - 1024   # words left beside s, n_iter, n_cigar, cigar_pairs and the headers
+        order = np.random.default_rng(0).permutation(len(nc))
+        keep = np.sort(order[:np.searchsorted(np.cumsum(nc[order].astype(np.int64)), budget, side="right")])
+        cigar_batch.fetch_cigars()
+        words = [cigar_batch.cigar(int(i), int(nc[i])) for i in keep]
+        arrays["cigar"] = np.concatenate(words) if words else np.zeros(0, dtype=np.uint32)
+        arrays["cigar_pairs"] = np.asarray(ids, dtype=np.int64)[keep]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return sorted(name + ".npy" for name in arrays)
 
 
 def main():
@@ -725,6 +767,7 @@ def main():
 
     kernel_ms, retries, step_no = [], 0, 0
     per_seed_kernel = [[] for _ in batches]
+    gathered = [None]                          # at N > 1: the records of all ranks from the last step's gather
 
     def step(record: bool):
         nonlocal retries, step_no
@@ -735,7 +778,7 @@ def main():
         res = bk.results()                     # (s, n_iter) records on the host; re-runs of pairs that did not fit happen here
         retries += eng.stats().n_retries
         if world > 1:                          # the result gather of the multi-GPU job: one RCCL all_gather over xGMI
-            gather_records(dist, d_s, d_it, n_total, device=dev, deal=deal)
+            gathered[0] = gather_records(dist, d_s, d_it, n_total, device=dev, deal=deal)
         if record:
             kernel_ms.append(eng.stats().kernel_ms)
             per_seed_kernel[k].append(eng.stats().kernel_ms)
@@ -752,23 +795,31 @@ def main():
     retries, step_no = 0, 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(False)
+        last = step(False)
     fence()
     elapsed = time.perf_counter() - t0
     timed_retries = retries
     timed_bases = sum(rot[i % len(rot)][0].bases for i in range(args.steps))
-    # kernel-only timing (HIP events recorded by the library on the launch stream), outside the wall-clock region
-    step_no = 0
-    cells_seed = [0] * len(batches)
-    s = n_iter = None
-    for i in range(max(3, min(args.steps, 10)) // len(batches) * len(batches) or len(batches)):
-        s_i, n_iter_i, _ = step(True)
-        cells_seed[i % len(batches)] = int(n_iter_i.sum())
-        assert (s_i >= 0).all(), "some pairs did not finish"
-        if i % len(batches) == 0:
-            s, n_iter = s_i.copy(), n_iter_i.copy()   # the first batch of the rotation: what cpu_baseline compares with
-    cells = int(round(sum(cells_seed) / len(cells_seed)))   # per launch, mean over the rotation
+    assert (last[0] >= 0).all(), "some pairs did not finish"
+    if args.dump_outputs and rank == 0:
+        last_k = (args.steps - 1) % len(batches)      # the batch the last timed step aligned
+        files = dump_outputs(args.dump_outputs, last, batches[last_k][0] if args.cigar else None, my_ids,
+                             None if gathered[0] is None else [x.cpu().numpy() for x in gathered[0]])
     st = eng.stats()
+    cells = 0
+    if args.full:
+        # kernel-only timing (HIP events recorded by the library on the launch stream), outside the wall-clock region
+        step_no = 0
+        cells_seed = [0] * len(batches)
+        s = n_iter = None
+        for i in range(max(3, min(args.steps, 10)) // len(batches) * len(batches) or len(batches)):
+            s_i, n_iter_i, _ = step(True)
+            cells_seed[i % len(batches)] = int(n_iter_i.sum())
+            assert (s_i >= 0).all(), "some pairs did not finish"
+            if i % len(batches) == 0:
+                s, n_iter = s_i.copy(), n_iter_i.copy()   # the first batch of the rotation: what cpu_baseline compares with
+        cells = int(round(sum(cells_seed) / len(cells_seed)))   # per launch, mean over the rotation
+        st = eng.stats()
 
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -785,28 +836,12 @@ def main():
             dist.destroy_process_group()
         return
 
-    k_ms = float(np.mean(kernel_ms))
-    bytes_per_cell = 49 if args.cigar else ALGO_BYTES_PER_CELL
     mode = "score+CIGAR high-mem" if args.cigar else "score-only"
     if strong:
         workload = (f"{n_total} pairs in total x {args.tl} bp, {args.div:g} divergence, {mode} mwf_wfa_exact, default penalties, dealt over "
                     f"{world} GPU(s) (BASELINE configs[4])")
     else:
         workload = (f"{args.pairs} pairs/GPU x {args.tl} bp, {args.div:g} divergence, {mode} mwf_wfa_exact, default penalties (BASELINE configs[2])")
-    # What the kernel itself must move per cell (the floor of ITS traffic): the band kernels keep E1/F1/E2/F2 in registers,
-    # so only H crosses HBM (three loads + one store per cell: 16 bytes, 8 with the packed kernel's 16-bit rows), +1 traceback byte;
-    # the generic kernel with E2/F2 in LDS moves 32 of the 48, 16 with its 16-bit ring rows.
-    if st.kernel_kind == 2:
-        kb = (8 if st.packed else 16) + (1 if args.cigar else 0)
-    elif st.kernel_kind == 0:
-        kb = (16 if st.packed == 16 else 32) + (1 if args.cigar else 0)   # 16-bit ring rows: H (three loads, one store) + E1/F1 (load + store each) at 2 bytes
-    else:
-        kb = 16 + (1 if args.cigar else 0)
-    key = f"{pk.n}x{args.tl}@{args.div:g}{'c' if args.cigar else 's'}"
-    rf = counter_roofline(k_ms * 1e-3, TRAFFIC.get(key, {}), float(kb) * cells, float(bytes_per_cell) * cells, f"{bytes_per_cell} B x cells", ran_symbol(st))
-    rf.update({"kernel_bytes_per_cell": kb, "cells_per_launch": cells, "kernel_ms": k_ms,
-               "note": "frac = counter traffic / kernel time / 8 TB/s (the same definition in long_pairs.*.roofline and long_batches.roofline). Nothing physical binds "
-                       "this kernel: what is left is per-penalty synchronisation (wait_any_over_wave_cycles) and single-wave issue latency (DESIGN.md section 4)."})
     out = {
         "metric": "aligned Gbp/s (q+t)",
         "value": total_timed_bases / elapsed / 1e9,
@@ -815,9 +850,9 @@ def main():
         "ms_per_step": elapsed / args.steps * 1e3,
         # Which reading of BASELINE's metric `value` is: the measurement contract's (inputs already resident in HBM when the timed region
         # starts; results on the host when it ends).  SURVEY 8(d)'s reading — host buffers in to host results out, H2D + kernels + D2H — is
-        # the top-level `end_to_end` block of this line (same batches, same run), never `value`.
+        # the top-level `end_to_end` block of a --full line (same batches, same run), never `value`.
         "value_definition": "resident: sequences in HBM before the clock starts, alignment kernels + (s, n_iter) records on the host (+ the RCCL gather at N > 1) inside it; "
-                            "SURVEY 8(d)'s host-to-host figure is `end_to_end.gbps`",
+                            "SURVEY 8(d)'s host-to-host figure is `end_to_end.gbps` (--full)",
         "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
         # the arithmetic the timed kernel computes in (results are bit-exact to the reference's int32 either way)
         "dtype": ("int16x2 packed, range-guarded (bit-exact to the reference's int32)" if (st.kernel_kind == 2 and st.packed) else
@@ -826,22 +861,45 @@ def main():
         "config": {
             "workload": workload,
             "pairs_this_gpu": pk.n, "pairs_total": n_total, "target_len": args.tl, "divergence": args.div,
-            "bases_this_gpu": pk.bases, "cells_this_gpu": cells, "mean_s": float(s.mean()),
+            "bases_this_gpu": pk.bases,
             "step": "alignment kernels on sequences already resident in HBM when the timed region starts (the measurement contract's `value`; the host-buffers-in "
                     "to host-results-out rate of the same batch is `end_to_end_gbps`) + (s, n_iter) records to the host" + (" + RCCL all_gather of the records" if world > 1 else ""),
             "kernel": KERNEL_NAMES.get(3 if (st.kernel_kind == 2 and st.packed) else st.kernel_kind, "?"), "grid": st.grid, "block": st.block,
             "parallelism": f"pairs dealt over {world} GPU(s), no data-path collective, one RCCL all_gather of (s,n_iter)",
         },
-        "gcells_per_s": total_cells * args.steps / elapsed / 1e9,
-        "seeds": {"n": len(batches), "base_seeds": [args.seed + 10000 * k for k in range(len(batches))],
-                  "kernel_ms_per_seed": [float(np.mean(x)) if x else None for x in per_seed_kernel],
-                  "note": "the timed steps rotate through these batches: `value`, `ms_per_step` and roofline.kernel_ms are means over them"},
-        "kernel_gbps": pk.bases / (k_ms * 1e-3) / 1e9,
         "n_retries": timed_retries,
-        "roofline": rf,
     }
+    if args.dump_outputs:
+        out["outputs"] = {"dir": args.dump_outputs, "files": files,
+                          "what": f"the records of the last timed step (batch of base seed {args.seed + 10000 * last_k}) as float64"}
+    if args.full:
+        k_ms = float(np.mean(kernel_ms))
+        bytes_per_cell = 49 if args.cigar else ALGO_BYTES_PER_CELL
+        # What the kernel itself must move per cell (the floor of ITS traffic): the band kernels keep E1/F1/E2/F2 in registers,
+        # so only H crosses HBM (three loads + one store per cell: 16 bytes, 8 with the packed kernel's 16-bit rows), +1 traceback byte;
+        # the generic kernel with E2/F2 in LDS moves 32 of the 48, 16 with its 16-bit ring rows.
+        if st.kernel_kind == 2:
+            kb = (8 if st.packed else 16) + (1 if args.cigar else 0)
+        elif st.kernel_kind == 0:
+            kb = (16 if st.packed == 16 else 32) + (1 if args.cigar else 0)   # 16-bit ring rows: H (three loads, one store) + E1/F1 (load + store each) at 2 bytes
+        else:
+            kb = 16 + (1 if args.cigar else 0)
+        key = f"{pk.n}x{args.tl}@{args.div:g}{'c' if args.cigar else 's'}"
+        rf = counter_roofline(k_ms * 1e-3, TRAFFIC.get(key, {}), float(kb) * cells, float(bytes_per_cell) * cells, f"{bytes_per_cell} B x cells", ran_symbol(st))
+        rf.update({"kernel_bytes_per_cell": kb, "cells_per_launch": cells, "kernel_ms": k_ms,
+                   "note": "frac = counter traffic / kernel time / 8 TB/s (the same definition in long_pairs.*.roofline and long_batches.roofline). Nothing physical binds "
+                           "this kernel: what is left is per-penalty synchronisation (wait_any_over_wave_cycles) and single-wave issue latency (DESIGN.md section 4)."})
+        out["config"].update({"cells_this_gpu": cells, "mean_s": float(s.mean())})
+        out.update({
+            "gcells_per_s": total_cells * args.steps / elapsed / 1e9,
+            "seeds": {"n": len(batches), "base_seeds": [args.seed + 10000 * k for k in range(len(batches))],
+                      "kernel_ms_per_seed": [float(np.mean(x)) if x else None for x in per_seed_kernel],
+                      "note": "the timed steps rotate through these batches: `value`, `ms_per_step` and roofline.kernel_ms are means over them"},
+            "kernel_gbps": pk.bases / (k_ms * 1e-3) / 1e9,
+            "roofline": rf,
+        })
 
-    if world == 1 and args.extras:
+    if args.full and world == 1 and args.extras:
         out["peak_device_bytes"] = int(st.dev_bytes_peak)
         # ---- host buffers in -> host results out (PCIe both ways), warmed, pooled allocations — reported beside, never as `value`
         try:
@@ -865,7 +923,7 @@ def main():
             out["end_to_end_gbps"] = repr(e)
 
     # ---- CPU baseline: same pairs (a bounded sample), host cores of this box
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         from oracle.pyoracle import Oracle, Reference, make_opt
         n = min(args.cpu_sample, pk.n)
         cores = host_cores()
@@ -917,7 +975,7 @@ def main():
     for bk, _, _ in batches:
         bk.free()
     eng.close()
-    if world == 1 and args.extras:
+    if args.full and world == 1 and args.extras:
         try:
             out["call_latency_us"] = call_latency(mw, synth_pair)
         except Exception as e:  # never lose the headline line over the extras

@@ -8,7 +8,7 @@ OUT=gpurun_out/icache_$TAG; rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 P='import json,sys; d=json.load(sys.stdin); print("%.3f ms kernel, grid %d block %d retries %d" % (d["roofline"]["kernel_ms"], d["config"]["grid"], d["config"]["block"], d["n_retries"]))'
 for A in "--pairs 256" "--pairs 512" "--pairs 1024" "--pairs 1024 --slots-per-cu 1" "--pairs 1024 --cigar"; do
-  echo -n "$A: "; timeout 200 python bench.py --extras 0 --cpu-sample 0 --steps 5 $A 2>&1 | tail -1 | python -c "$P"
+  echo -n "$A: "; timeout 200 python bench.py --full --extras 0 --cpu-sample 0 --steps 5 $A 2>&1 | tail -1 | python -c "$P"
 done 2>&1 | tee "$OUT/coresidency.txt"
 rocprofv3 -L 2>/dev/null | grep -i -o "SQC_[A-Z_0-9]*\|SQ_IFETCH[A-Z_0-9]*\|SQ_INST_LEVEL[A-Z_0-9]*" | sort -u | tr '\n' ' ' > "$OUT/avail.txt"; cat "$OUT/avail.txt"; echo
 BENCH="python bench.py --steps 3 --warmup 1 --cpu-sample 0 --extras 0"

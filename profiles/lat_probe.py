@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0,'/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, miniwfa_amd as mw
 from miniwfa_amd.synth import synth_pair, PackedBatch
 pairs=[synth_pair(50000+i,10000,0.05) for i in range(1024)]

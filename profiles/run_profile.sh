@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 3 --warmup 1 --cpu-sample 0 --extras 0 $*"
+BENCH="python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --extras 0 $*"
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o t -- $BENCH > "$OUT/bench_trace.json" 2> "$OUT/trace.err"
 # PMC passes, each alone with kernel-trace only (MI355X_MICROARCH.md: FETCH_SIZE 3 TCC slots, WRITE_SIZE 2)
 for PMC in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_INSTS_SMEM GRBM_GUI_ACTIVE" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do

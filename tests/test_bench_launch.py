@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,3 +85,125 @@ def test_bench_reads_the_real_pairs_when_they_are_dropped_in(tmp_path):
     assert bench.read_first_fasta(str(fa)) == b"ACGTacgtN"
     assert bench.read_first_fasta(str(fq)) == b"GATTACA"
     assert bench.REAL_PAIRS["c4_like_150kb"][1] == 26917 and bench.REAL_PAIRS["mhc_like_5Mb"][1] == 229868
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_full_is_off_by_default_and_steps_must_be_positive():
+    bench = _bench_module()
+    a = bench.parse_args(["--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dry_run_dumps_the_gathered_records(tmp_path):
+    """--dump-outputs on the CPU dry run: every pair's (s, n_iter) as float64 .npy, equal to the oracle's, the same from run to run."""
+    from miniwfa_amd.synth import synth_pair
+    from oracle.pyoracle import Oracle, make_opt
+    got = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = _run(["--gpus", "2", "--steps", "1", "--dump-outputs", str(d)], {"MWF_BENCH_BACKEND": "gloo"})
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        assert sorted(os.listdir(d)) == ["n_iter.npy", "s.npy"]
+        got.append({n: np.load(d / f"{n}.npy") for n in ("s", "n_iter")})
+    s, it = got[0]["s"], got[0]["n_iter"]
+    assert s.dtype == np.float64 and it.dtype == np.float64 and len(s) == len(it) == 32    # 2 ranks x 16 pairs
+    orc, o = Oracle(), make_opt()
+    for i in range(len(s)):
+        es, eit, _ = orc.align(*synth_pair(50000 + i, 300, 0.05), o)
+        assert (s[i], it[i]) == (es, eit), i
+    assert all((got[1][n] == got[0][n]).all() for n in ("s", "n_iter"))
+
+
+class _FakeCigarBatch:
+    def __init__(self, nc):
+        self.nc, self.fetched = nc, False
+
+    def fetch_cigars(self):
+        self.fetched = True
+
+    def cigar(self, i, n):
+        assert self.fetched and n == self.nc[i]
+        return np.arange(n, dtype=np.uint32) + np.uint32(1000 * i)
+
+
+def test_dump_outputs_cigars_and_their_cap(tmp_path, monkeypatch):
+    bench = _bench_module()
+    rng = np.random.default_rng(5)
+    n = 200
+    nc = rng.integers(0, 60, n).astype(np.int32)
+    last = (rng.integers(0, 999, n).astype(np.int32), rng.integers(0, 10 ** 9, n).astype(np.int64), nc)
+    ids = np.arange(n) + 400
+    # everything fits: every pair's words, in pair order
+    files = bench.dump_outputs(str(tmp_path / "all"), last, _FakeCigarBatch(nc), ids)
+    assert files == ["cigar.npy", "cigar_pairs.npy", "n_cigar.npy", "n_iter.npy", "s.npy"]
+    a = {f[:-4]: np.load(tmp_path / "all" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert (a["s"] == last[0]).all() and (a["n_iter"] == last[1]).all() and (a["n_cigar"] == nc).all()
+    assert (a["cigar_pairs"] == ids).all()
+    assert (a["cigar"] == np.concatenate([np.arange(c) + 1000 * i for i, c in enumerate(nc)])).all()
+    # a cap smaller than that: a fixed sample of whole pairs, the files within the cap, the same sample every time
+    cap = 8 * (5 * n + 2500)
+    monkeypatch.setattr(bench, "DUMP_BYTES_CAP", cap)
+    picks = []
+    for k in range(2):
+        d = tmp_path / f"cap{k}"
+        bench.dump_outputs(str(d), last, _FakeCigarBatch(nc), ids)
+        b = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= cap
+        keep = b["cigar_pairs"].astype(np.int64) - 400
+        assert 0 < len(keep) < n and (np.diff(keep) > 0).all()
+        assert (b["cigar"] == np.concatenate([np.arange(nc[i]) + 1000 * i for i in keep])).all()
+        picks.append(keep)
+    assert (picks[0] == picks[1]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cigar", [False, True])
+def test_plain_run_line_and_dumped_outputs(tmp_path, cigar):
+    """A plain run prints the headline fields only (nothing that takes runs of its own), `steps` is what was asked, and --dump-outputs holds
+    the last timed step's records of its batch, equal to the oracle's."""
+    from miniwfa_amd.synth import synth_pair
+    from oracle.pyoracle import Oracle, make_opt
+    d = tmp_path / "out"
+    r = _run(["--steps", "3", "--warmup", "1", "--seeds", "1", "--pairs", "24", "--len", "1500", "--dump-outputs", str(d)] + (["--cigar"] if cigar else []),
+             timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    for k in ("roofline", "cpu_baseline", "kernel_gbps", "end_to_end", "long_pairs", "call_latency_us"):
+        assert k not in line, k
+    a = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert sorted(a) == (["cigar", "cigar_pairs", "n_cigar", "n_iter", "s"] if cigar else ["n_iter", "s"])
+    orc, o = Oracle(), make_opt(flag=1 if cigar else 0)
+    words = []
+    for i in range(24):
+        es, eit, ecig = orc.align(*synth_pair(50000 + i, 1500, 0.05), o)
+        assert (a["s"][i], a["n_iter"][i]) == (es, eit), i
+        if cigar:
+            assert a["n_cigar"][i] == len(ecig), i
+            words += ecig
+    if cigar:
+        assert (a["cigar_pairs"] == np.arange(24)).all() and (a["cigar"] == np.asarray(words, dtype=np.float64)).all()
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_side_measurements():
+    r = _run(["--full", "--extras", "0", "--cpu-sample", "0", "--steps", "4", "--warmup", "1", "--pairs", "24", "--len", "1500"], timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    line = _json_lines(r.stdout)[-1]
+    assert line["steps"] == 4 and line["roofline"]["kernel_ms"] > 0 and line["kernel_gbps"] > 0 and line["config"]["cells_this_gpu"] > 0
