@@ -137,7 +137,11 @@ void mwf_gpu_batch_free(mwf_gpu_batch_t *b);
 /* Align every pair of the batch with `opt`.  Kernels are enqueued on the engine's stream; the call
  * returns after they are enqueued — except on the whole-device kernel (a few long pairs), whose launches are serialised
  * per device and waited for.  Pairs that need a re-run get it in mwf_gpu_batch_results().  Returns 0, or a negative
- * error (see mwf_gpu_last_error). */
+ * error (see mwf_gpu_last_error).
+ * The first align of a batch (and the first after its options or the engine's tunables change) plans it: in a batch of
+ * more long pairs than the device holds at once it also reads every pair's sequences for an 8-mer work estimate (one small
+ * kernel and one wait) and deals the pairs by it.  That order is a scheduling hint kept with the plan: if a wrapped
+ * batch's contents change later, it costs speed, never correctness. */
 int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt);
 
 /* Wait for the batch and copy the fixed-size results to host arrays of length n (any may be NULL). */

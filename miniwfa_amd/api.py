@@ -130,6 +130,8 @@ def lib() -> C.CDLL:
     L.mwf_gpu_set.restype = C.c_int
     L.mwf_gpu_test_hook.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.mwf_gpu_test_hook.restype = C.c_int
+    L.mwf_gpu_test_pair_sketch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_test_pair_sketch.restype = C.c_int
     L.mwf_gpu_debug_band.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), C.c_int32, C.c_void_p, C.c_int32]
     L.mwf_gpu_debug_band.restype = C.c_int32
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
@@ -402,6 +404,13 @@ class Batch:
         rc = lib().mwf_gpu_batch_fetch_cigars(self.eng.h, self.h)
         if rc != 0:
             raise RuntimeError(f"CIGAR download failed ({rc}): " + self.eng.error())
+
+    def work_sketch(self) -> np.ndarray:
+        """hits[i]: 8-mers of pair i's query that occur in its target — the per-pair work estimate the band classes are dealt by (test hook)."""
+        out = np.zeros(max(1, self.n), dtype=np.int32)
+        if lib().mwf_gpu_test_pair_sketch(self.eng.h, self.h, out.ctypes.data) != 0:
+            raise RuntimeError("pair sketch failed: " + self.eng.error())
+        return out[:self.n]
 
     def debug_band(self, opt: MwfOpt, pair: int, cap: int = 1 << 20):
         """[(lo, hi)] in DIAGONAL coordinates of every slice the core pass opened for `pair` (diagnostics)."""

@@ -122,6 +122,8 @@ int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "coop_grid")) g->coop_grid_cap = (int)std::max<int64_t>(0, value);
 	else if (!strcmp(name, "sys_p") && sys_p_supported((int)value)) g->sys_p = (int)value; // (8; 4 and 16 only in builds with -DMWF_SYS_ALL_P)
 	else if (!strcmp(name, "sys_c") && (value == 0 || sys_c_supported((int)value))) g->sys_c = (int)value; // (2: builds with -DMWF_SYS_C2 only)
+	else if (!strcmp(name, "work_order") && value >= 0 && value <= 3) g->work_order = (int)value;
+	else if (!strcmp(name, "timeline")) g->timeline = (int64_t*)(intptr_t)value; // (a device array of 4 int64 per pair of every batch aligned while it is set; 0: off)
 	else return -1;
 	++g->tun_gen;
 	return 0;
@@ -236,6 +238,20 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
 	const int32_t n = std::min<int32_t>(cap, std::max(0, b->h_s[pair] >= 0 ? b->h_s[pair] : 0));
 	if (n > 0) HIP_TRY(g, hipMemcpy(lohi, g->dbg.p, (size_t)n * 8, hipMemcpyDeviceToHost));
 	return n;
+}
+
+/* test hook: the per-pair work sketch the band classes are dealt by (mwf_plan.cpp), for every pair of the batch: hits[i] = 8-mers of pair i's query
+   that occur in its target.  Exported for tests/ and profiles/, not declared in include/miniwfa.h. */
+int mwf_gpu_test_pair_sketch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *hits)
+{
+	if (!g || !b || !hits) return -1;
+	(void)hipSetDevice(g->device);
+	if (b->busy) HIP_TRY(g, hipStreamSynchronize(g->stream)); // (the scratch it writes is the results' debug area)
+	if (b->n == 0) return 0;
+	if (launch_pair_sketch(b->d_seqs, b->d_t_off, b->d_tl, b->d_q_off, b->d_ql, nullptr, b->n, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
+	HIP_TRY(g, hipMemcpyAsync(hits, b->d_dbg4, (size_t)b->n * 4, hipMemcpyDeviceToHost, g->stream));
+	HIP_TRY(g, hipStreamSynchronize(g->stream));
+	return 0;
 }
 
 /* ------------------------------------------------------------------ drop-in entry points */

@@ -73,6 +73,9 @@ struct mwf_gpu_s {
 	int64_t coop_min_len = 0;
 	int64_t tb_budget_mb = 0;   // 0: automatic
 	int force_kind = -1;
+	int work_order = 1;         // deal order of the band classes on the shared work counter (mwf_plan.cpp): 0 length, 1 predicted work (per-pair 8-mer sketch),
+	                            // 2 the n_iter of the batch's previous align (the bound a prediction can reach), 3 shortest first — mwf_gpu_test_hook "work_order"
+	int64_t *timeline = nullptr; // mwf_gpu_test_hook "timeline": device array of [pair][4] int64 that a probe build of the packed band kernel fills (BatchArgs::timeline)
 	int res_pin_on = 1;        // small score-only batches: results written straight into pinned host memory (0: always copied back)
 	int lane_chunks = 0;       // its window: 64-column chunks of LDS rows (1-4; 0: three for pairs of up to 400 bases of target + query, else four); a penalty only passes over the chunks the window has reached
 	int lane_max_len = 325;    // (weighed by the batch's divergence / 5 % where known.  Round 3 set 400 against the band kernel of that round; against round 6's 64-thread geometry the lane kernel
@@ -223,6 +226,7 @@ mwf_gpu_batch_t *batch_common(mwf_gpu_t *g, int32_t n, const int32_t *h_tl, cons
 mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, const char *const *ts, const int32_t *ql, const char *const *qs,
                                  const char *packed, int64_t packed_bytes, const int64_t *p_t_off, const int64_t *p_q_off);
 float estimate_divergence_device(mwf_gpu_t *g, mwf_gpu_batch_t *b);
+double sketch_divergence(int32_t hit, int32_t tot, int32_t lt); // one pair's divergence from the hits of its query's `tot` 8-mers in a target of lt bases
 extern "C" int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value); // mwf_engine.cpp: forced kernels / geometries / failure paths for tests/ and profiles/
 // ---- mwf_async.cpp: submit / wait and the opt-in coalescing of single calls
 int64_t coalesce_window_us();

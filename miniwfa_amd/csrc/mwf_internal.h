@@ -133,6 +133,8 @@ struct BatchArgs {
 	                           // one atomic on cig_head per pair is ~12.7 ns on a single address); 0: one allocation per pair, no holes
 	int32_t lane_chunks;       // one-diagonal-per-lane kernels: 64-column chunks of their LDS rows (mwf_lane.hip: 1-4; mwf_mid.hip: its span / 64)
 	int32_t sys_coop_launch;   // host side only: 1 = launch through hipLaunchCooperativeKernel (the runtime then guarantees that every workgroup is resident)
+	int64_t *timeline;         // packed band kernel, profiles only (null otherwise): [pair][4] wall clock (100 MHz) when its workgroup took it and when it was
+	                           // done, the CU (__smid) and the workgroup — one record per pair, never per penalty (mwf_gpu_test_hook "timeline")
 };
 
 // launch wrappers implemented in mwf_kernels.hip (generic kernel: any penalties, any band, low-memory mode)
@@ -140,6 +142,9 @@ int launch_reset(int32_t *status, int32_t *s, int32_t n, unsigned long long *cig
 int launch_batch(const BatchArgs &a, int grid, int block, void *stream);
 // 8-mer sketch of `samples` (<= 16) pairs of a device-resident batch: out[k] = 8-mers of pair (k n / samples)'s query prefix that occur in its target prefix
 int launch_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, int32_t n, int32_t samples, int32_t *out, void *stream);
+// the same statistic over the WHOLE sequences of every pair order[0 .. n) (order null: pairs 0 .. n; one workgroup each): out[k] = 8-mers of that pair's query that occur
+// in its target (the work estimate the band classes are dealt by, mwf_plan.cpp)
+int launch_pair_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, const int32_t *order, int32_t n, int32_t *out, void *stream);
 int  bigring_kernel_occupancy();                      // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
 int  batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ring16);   // resident workgroups per CU for that block size
 

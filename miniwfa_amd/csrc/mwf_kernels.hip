@@ -1221,17 +1221,12 @@ __device__ __forceinline__ uint32_t sketch_kmer(const uint8_t *p)
 	for (int i = 0; i < kSketchK; ++i) h = (h << 2) | ((p[i] >> 1) & 3u);
 	return h;
 }
-__global__ __launch_bounds__(256) void sketch_kernel(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql,
-                                                      int32_t n, int32_t samples, int32_t *out)
+// hits of the query's 8-mers in the target: the calling workgroup's 256 threads, the 4^8-bit set in LDS; the count lands in *hits
+__device__ __forceinline__ void sketch_hits(const uint8_t *t, int32_t lt, const uint8_t *q, int32_t lq, uint32_t *bits, int32_t *hits)
 {
-	__shared__ uint32_t bits[(1 << (2 * kSketchK)) / 32];
-	__shared__ int32_t hits;
-	const int32_t i = (int32_t)((int64_t)blockIdx.x * n / samples);
-	const int32_t lt = min(tl[i], kSketchLen), lq = min(ql[i], kSketchLen);
 	for (int32_t j = threadIdx.x; j < (1 << (2 * kSketchK)) / 32; j += 256) bits[j] = 0;
-	if (threadIdx.x == 0) hits = 0;
+	if (threadIdx.x == 0) *hits = 0;
 	__syncthreads();
-	const uint8_t *t = seqs + t_off[i], *q = seqs + q_off[i];
 	for (int32_t j = threadIdx.x; j + kSketchK <= lt; j += 256) {
 		const uint32_t h = sketch_kmer(t + j);
 		atomicOr(&bits[h >> 5], 1u << (h & 31));
@@ -1242,14 +1237,43 @@ __global__ __launch_bounds__(256) void sketch_kernel(const uint8_t *seqs, const 
 		const uint32_t h = sketch_kmer(q + j);
 		mine += (int32_t)((bits[h >> 5] >> (h & 31)) & 1u);
 	}
-	if (mine) atomicAdd(&hits, mine);
+	if (mine) atomicAdd(hits, mine);
 	__syncthreads();
+}
+__global__ __launch_bounds__(256) void sketch_kernel(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql,
+                                                      int32_t n, int32_t samples, int32_t *out)
+{
+	__shared__ uint32_t bits[(1 << (2 * kSketchK)) / 32];
+	__shared__ int32_t hits;
+	const int32_t i = (int32_t)((int64_t)blockIdx.x * n / samples);
+	sketch_hits(seqs + t_off[i], min(tl[i], kSketchLen), seqs + q_off[i], min(ql[i], kSketchLen), bits, &hits);
 	if (threadIdx.x == 0) out[blockIdx.x] = hits;
 }
 
 int launch_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, int32_t n, int32_t samples, int32_t *out, void *stream)
 {
 	hipLaunchKernelGGL(sketch_kernel, dim3(samples), dim3(256), 0, (hipStream_t)stream, seqs, t_off, tl, q_off, ql, n, samples, out);
+	return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- per-pair work sketch (mwf_plan.cpp: the deal order of the band classes on the shared work counter).  A pair's penalty s — and with it the
+// penalties its workgroup runs — grows with its divergence, and an equal-length batch at 5 % holds pairs of s 2118 ... 2838: dealt by length, the
+// last ones finish far apart while CUs idle.  The same statistic as sketch_kernel over the WHOLE sequences (a 1500-base prefix correlates 0.34 with s,
+// the whole pair 0.88): one workgroup per pair order[k] (order null: pair k), out[k] = hits.  ~20 kB read per 10 kb pair, once per plan.
+__global__ __launch_bounds__(256) void pair_sketch_kernel(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql,
+                                                           const int32_t *order, int32_t *out)
+{
+	__shared__ uint32_t bits[(1 << (2 * kSketchK)) / 32];
+	__shared__ int32_t hits;
+	const int32_t i = order ? order[blockIdx.x] : (int32_t)blockIdx.x;
+	sketch_hits(seqs + t_off[i], tl[i], seqs + q_off[i], ql[i], bits, &hits);
+	if (threadIdx.x == 0) out[blockIdx.x] = hits;
+}
+
+int launch_pair_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, const int32_t *order, int32_t n, int32_t *out, void *stream)
+{
+	if (n <= 0) return 0;
+	hipLaunchKernelGGL(pair_sketch_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, seqs, t_off, tl, q_off, ql, order, out);
 	return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

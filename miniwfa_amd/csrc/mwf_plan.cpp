@@ -311,6 +311,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 	memset(&a, 0, sizeof(a));
 	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
 	a.order = d_order, a.n_pairs = n_items;
+	a.timeline = g->timeline;
 	// A launch of one workgroup per pair on the kernels that take it (lane, mid, packed band) needs no work counter: workgroup i aligns
 	// pair i.  Otherwise a fresh counter: the first kQueueSlots launches of an align call use the ones its reset kernel zeroed.
 	// The lane kernel takes a set of 64 counters (kLaneCounters above).
@@ -934,7 +935,8 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 			G.max_tl = std::max<int64_t>(G.max_tl, tl), G.max_exp_win = std::max(G.max_exp_win, exp_win);
 			G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, ((tl + 3) & ~3LL) + 8 + ((ql + 3) & ~3LL) + 16);
 		}
-		// The processing order: groups in run order, longest first inside a group (the persistent workgroups finish together).  h_order is
+		// The processing order: groups in run order, longest first inside a group (the persistent workgroups finish together; the classes on the shared
+		// work counter then by predicted work, below).  h_order is
 		// already sorted longest first (batch_common) and that order is stable: one pass over it deals the pairs to their groups.
 		std::vector<int32_t> start(15, 0), order((size_t)b->n);
 		{
@@ -949,6 +951,43 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 			});
 		}
 		for (int32_t i : b->h_len_order) order[(size_t)start[cls[i]]++] = i;
+		// The classes on the shared work counter — the 512-thread geometries (1, its biased copy 14, its byte-wise copy 6) and the 1024-thread span
+		// geometry (13) — are dealt by predicted WORK, largest first: in an equal-length batch "longest first" says nothing about how long a pair takes.
+		// 1024 x 10 kb at 5 %: s 2118 ... 2838 (sd 118) on one length; the pairs dealt last finished far apart while CUs idled (the drain).
+		// The estimate: s ~ (tl + ql) x d, d from the share of the query's 8-mers found in the target over the WHOLE pair (correlation 0.88 with s;
+		// the batch sketch's 1500-base prefix 0.34).  A class that fits on the device at once (no more pairs than workgroups) has nothing to deal.
+		bool reorder = false;
+		for (int c : {13, 14, 1, 6}) reorder |= count[c] > 2 * g->n_cu; // (two workgroups per CU on the 512-thread geometries; the span geometry holds fewer)
+		if (reorder && g->work_order != 0 && (g->work_order != 2 || (int32_t)b->h_iter.size() == b->n)) {
+			const int32_t lo = start[13] - count[13], hi = start[6]; // (run_order keeps the four side by side)
+			std::vector<double> key((size_t)b->n, 0.0);
+			if (g->work_order == 1) {
+				// one workgroup per pair reads both sequences from the device (at align: the caller's arrays need only be valid then); the pair ids go up in
+				// the order array, which gets the final order below
+				if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{order.data() + lo, (size_t)(hi - lo) * 4}})) return -1;
+				b->h_order.clear();
+				if (launch_pair_sketch(b->d_seqs, b->d_t_off, b->d_tl, b->d_q_off, b->d_ql, b->d_order, hi - lo, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
+				std::vector<int32_t> hits((size_t)(hi - lo));
+				HIP_TRY(g, hipMemcpyAsync(hits.data(), b->d_dbg4, hits.size() * 4, hipMemcpyDeviceToHost, g->stream)); // (scratch behind the results: written by this align's kernels only with MWF_F_DEBUG)
+				HIP_TRY(g, hipStreamSynchronize(g->stream));
+				for (int32_t k = lo; k < hi; ++k) {
+					const int32_t i = order[(size_t)k], tl = b->h_tl[i], ql = b->h_ql[i];
+					key[(size_t)i] = (double)((int64_t)tl + ql) * sketch_divergence(hits[(size_t)(k - lo)], std::max(ql - 7, 0), tl);
+				}
+			} else if (g->work_order == 2) {
+				for (int32_t k = lo; k < hi; ++k) key[(size_t)order[(size_t)k]] = (double)b->h_iter[(size_t)order[(size_t)k]];
+			}
+			for (int c : {13, 14, 1, 6}) {
+				if (count[c] <= 2 * g->n_cu) continue;
+				const auto first = order.begin() + (start[c] - count[c]), last = order.begin() + start[c];
+				if (g->work_order == 3) std::reverse(first, last); // (shortest first: the other bound of the measurement)
+				else std::sort(first, last, [&](int32_t x, int32_t y) {
+					if (key[(size_t)x] != key[(size_t)y]) return key[(size_t)x] > key[(size_t)y];
+					const int64_t lx = (int64_t)b->h_tl[x] + b->h_ql[x], ly = (int64_t)b->h_tl[y] + b->h_ql[y];
+					return lx != ly ? lx > ly : x < y;
+				});
+			}
+		}
 		if (order != b->h_order) {
 			b->h_order.swap(order);
 			if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{b->h_order.data(), b->h_order.size() * 4}})) return -1; // (waits for earlier work on the stream first)
