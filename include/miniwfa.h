@@ -164,7 +164,7 @@ typedef struct {
 	int64_t cells;         /* (penalty,diagonal) cells computed by core passes (= sum of n_iter) */
 	int64_t cells_pass1;   /* cells computed by low-memory first passes (not part of n_iter) */
 	int32_t n_launches;    /* kernel launches issued */
-	int32_t n_retries;     /* pairs re-run with a larger traceback arena */
+	int32_t n_retries;     /* re-runs of pairs the kernel they ran on handed back, all causes counted: window beyond the kernel's span, 16-bit offset range, a base outside A/C/G/T, traceback arena, CIGAR pool (a pair can be re-run more than once) */
 	int32_t grid, block;   /* geometry of the dominant launch */
 	int32_t kernel_kind;   /* 0: one workgroup per pair (generic); 1: one pair across the whole device; 2: one workgroup per pair (band) */
 	int64_t dev_bytes;     /* device memory the engine holds now: workspace pools + recycled batch allocations (live batches hold their own) */

@@ -16,6 +16,8 @@
 //     v_swap, the three per-penalty flags travel as one LDS word, rows are loaded only for chunks that are active.
 // Results are bit-identical to the other kernels (tests/test_gpu_parity.py).
 #include <cstddef>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 #include "mwf_device.h"
 
@@ -988,6 +990,9 @@ void launch_variant(const BatchArgs &a, int grid, int lds, hipStream_t st)
 		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 		(void)hipGetLastError();
 	}
+	// diagnostics: which instantiation this launch is — the eight template arguments, as tests/band_matrix.py lists them — and how many pairs it was given
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] band2 launch: T %d K %d E1 %d E2 %d TB %d S2 %d BI4 %d FOLD %d, %d pairs, grid %d\n", T, K, E1, E2, (int)TB, (int)S2, (int)BI4, (int)FOLD, (int)a.n_pairs, grid);
 	hipLaunchKernelGGL((wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), dim3(grid), dim3(T), lds, st, a);
 }
 

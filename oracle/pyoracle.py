@@ -102,6 +102,8 @@ class Oracle(_Aligner):
         L.mwfo_cigar2score.restype = C.c_int32
         L.mwfo_band_trace.argtypes = [C.POINTER(Opt), C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.POINTER(C.c_int32), C.c_int32]
         L.mwfo_band_trace.restype = C.c_int32
+        L.mwfo_band_trace_far.argtypes = [C.POINTER(Opt), C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.mwfo_band_trace_far.restype = C.c_int32
         L.mwfo_free.argtypes = [C.c_void_p]
         L.mwfo_free.restype = None
         L.mwfo_opt_init.argtypes = [C.POINTER(Opt)]
@@ -155,6 +157,16 @@ class Oracle(_Aligner):
         buf = (C.c_int32 * (2 * cap))()
         n = self.lib.mwfo_band_trace(C.byref(opt), len(t), t, len(q), q, buf, cap)
         return [(buf[2 * i], buf[2 * i + 1]) for i in range(min(n, cap))]
+
+    def band_trace_far(self, t: bytes, q: bytes, opt: Opt, cap: int = 1 << 16):
+        """(lohi int32[n, 2], far int32[n]): the band of every penalty as band_trace gives it, and the furthest H offset of the slice
+        of penalty s - x (numpy arrays; ctypes drops the GIL inside the call, so several host threads can trace at once)."""
+        import numpy as np
+        lohi = np.empty((cap, 2), dtype=np.int32)
+        far = np.empty(cap, dtype=np.int32)
+        n = self.lib.mwfo_band_trace_far(C.byref(opt), len(t), t, len(q), q, lohi.ctypes.data, far.ctypes.data, cap)
+        assert n <= cap, (n, cap)
+        return lohi[:n].copy(), far[:n].copy()
 
     def batch(self, packed, opt: Opt, threads: int, exact_fn=None, n=None, arena=None):
         """Threaded (pthreads, one pair per thread at a time) batch over the first n pairs of a miniwfa_amd.synth.PackedBatch;

@@ -59,6 +59,23 @@ def compare(got, exp, label, pairs, bad, log, check_cigar=True):
     return n_bad
 
 
+def retry_bound(orc, pairs, kw, block, fold=1):
+    """How many pairs of a batch forced onto ONE band geometry (block 64 ... 768, or 1024: "band_span" 2) that geometry may hand back: those whose
+    oracle window exceeds its admission window or meets one of its documented hand-back rules, and pairs outside A/C/G/T on a 2-bit geometry
+    (tests/band_matrix.py: not_fit_count).  n_retries of such a batch must not exceed it: every other pair the geometry has to finish itself."""
+    import band_matrix as bm
+    return bm.not_fit_count(orc, pairs, kw, block, 5 if block == 1024 else 2 if block == 768 else 3, fold, span=block == 1024)
+
+
+def check_retries(got, bound, label, bad, log):
+    """... as a mismatch record when the bound is broken."""
+    n = int(got[3].n_retries)
+    if log:
+        print(f"   {label}: re-runs {n}, pairs the geometry may hand back {bound}", flush=True)
+    if n > bound:
+        bad.append((label, "re-runs", n, "exceed the pairs the geometry may hand back", bound))
+
+
 # ---- profiles/fuzz_fold.py: folded against unfolded form of the packed band kernel, and both against the oracle -------------------------
 def fuzz_fold(seed=1, n=400, log=False, long_sets=True, penalty_sets=None):
     """Shapes that move the window's start up (length-skewed and unrelated pairs, long gaps), fuzz pairs, 10-20 kb pairs; penalty sets
@@ -90,6 +107,8 @@ def fuzz_fold(seed=1, n=400, log=False, long_sets=True, penalty_sets=None):
                     elif block:
                         tun += [("force_kind", 2), ("block", block), ("band_pack", 1)]
                     res[fold] = run_engine(pk, dict(**kw), tun)
+                    if block:   # one geometry for the whole batch: what it may hand back bounds the re-runs
+                        check_retries(res[fold], retry_bound(orc, pairs, kw, block, fold), f"fold seed {seed} {name} {kw} block {block} band_fold {fold}", bad, log)
                 diff = np.nonzero((res[0][0] != res[1][0]) | (res[0][1] != res[1][1]))[0]
                 for i in diff:
                     bad.append((f"fold seed {seed} {name} {kw} block {block}", int(i), len(pairs[i][0]), len(pairs[i][1]),
@@ -178,7 +197,10 @@ def fuzz_band2(seed=1, n_pairs=240, log=False, blocks=(0, 64, 512, 768), modes=N
         exp = oracle_many(orc, pairs, make_opt(**kw))
         for block in blocks:
             tun = [("force_kind", 2), ("block", block), ("band_pack", 1)] if block else []
-            compare(run_engine(pk, kw, tun), exp, f"band2 seed {seed} {kw} block {block or 'auto'}", pairs, bad, log)
+            got = run_engine(pk, kw, tun)
+            compare(got, exp, f"band2 seed {seed} {kw} block {block or 'auto'}", pairs, bad, log)
+            if block and not kw.get("step"):   # (low-memory mode runs on the generic kernel)
+                check_retries(got, retry_bound(orc, pairs, kw, block), f"band2 seed {seed} {kw} block {block}", bad, log)
     return bad
 
 

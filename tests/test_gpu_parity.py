@@ -10,6 +10,7 @@ import miniwfa_amd as mw
 from miniwfa_amd.synth import synth_pair, fuzz_pairs, skewed_pairs, PackedBatch
 from conftest import load_golden, golden_inputs
 from oracle.pyoracle import make_opt, cigar_str as ocig
+from fuzzlib import retry_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -351,6 +352,9 @@ def test_band_kernel_against_oracle(block, pack, oracle):
                 assert b.cigar(i, int(nc[i])).tolist() == ecig, (block, i)
         if block <= 256:
             assert eng.stats().n_retries > 0   # the 3000/5000 bp pairs at 30 % do not fit 512 / 1280 / 2816 columns
+        # ... and no more pairs are handed back than the geometry may hand back by the oracle's band trace (tests/band_matrix.py): the others it finishes itself
+        may = retry_bound(oracle, pairs, {k: getattr(o, k) for k in OPT_KEYS}, block)
+        assert eng.stats().n_retries <= may, (block, o.flag, o.o2, o.x, eng.stats().n_retries, may)
         b.free()
     eng.close()
 
@@ -732,6 +736,9 @@ def test_packed_band_kernel_fuzz_against_oracle(block, oracle):
             assert (int(s[i]), int(it[i])) == (es, eit), (block, kw, i, len(t), len(q))
             if ecig is not None:
                 assert b.cigar(i, int(nc[i])).tolist() == ecig, (block, kw, i)
+        if block:   # forced onto one geometry: re-runs only of pairs that geometry may hand back by the oracle's band trace (tests/band_matrix.py)
+            may = retry_bound(oracle, pairs, kw, block)
+            assert eng.stats().n_retries <= may, (block, kw, eng.stats().n_retries, may)
         b.free()
         eng.close()
 
