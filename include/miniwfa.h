@@ -60,6 +60,10 @@ void mwf_opt_init(mwf_opt_t *opt);
  * own assert/panic paths): max(x, o1+e1, o2+e2) < 4096 (below 256 every kernel applies; from 256 on — gap-open costs in the
  * hundreds — the pairs run on the generic kernel's big-ring form, one column per lane), and tl+ql < 2^31-4 (columns
  * are 32-bit).  x, e1, e2 >= 1 and o1, o2 >= 0, as the reference requires implicitly (miniwfa.c:390-392).
+ * Every penalty set gives the reference's answer; which kernels serve it depends on the gap extensions (e1, e2): the whole-device kernel for
+ * long pairs ("coop_min_len" below) takes (2,1), (2,2), (1,1) and e1 in {3, 4} with e2 in {1, 2} (minimap2's asm5 / asm20-like sets); under any
+ * other pair of extensions long pairs run on the generic one-workgroup-per-pair kernel (about ten times slower on a 150 kb pair).  The packed
+ * band kernel for big batches of mid-size pairs takes (2,1), (2,2), (1,1) only; other sets run such batches on the generic kernel.
  * Device: MWF_DEVICE=<ordinal> (default 0).  Any number of host threads may call concurrently. */
 void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r);
 
@@ -181,7 +185,8 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
 /* Tunables (call before align; every call invalidates the cached plans of the engine's batches).  Thirteen names and one action:
  *   "tb_budget_mb"      traceback arena of the one-workgroup-per-pair kernels (0 = automatic: four fifths of what is free, at most a quarter of the device)
  *   "lowmem_budget_mb"  whole-device kernel, opt.step > 0: a first-pass traceback above this many MB switches to the two-pass form whose first pass stores none (0 = a quarter of the device)
- *   "coop_min_len"      tl + ql from which a batch of at most sixteen pairs runs on the whole-device kernel (0 = 20 000 score-only, 15 000 with CIGAR)
+ *   "coop_min_len"      tl + ql from which a batch of at most sixteen pairs runs on the whole-device kernel (0 = 20 000 score-only, 15 000 with CIGAR);
+ *                       applies to the gap extensions that kernel is built for — (2,1), (2,2), (1,1), (3,1), (3,2), (4,1), (4,2) —, others stay on the generic kernel
  *   "seq2bit"           1 (default): pairs of plain A/C/G/T are held at 2 bits per base in LDS, any other pair runs on the byte-wise copy; 0: always bytes
  *   "ring16"            generic kernel: 1 (default) = 16-bit ring rows while target length + penalty fits 16 bits (half the HBM traffic); 0: always 32-bit rows
  *   "band_span"         1 (default): pairs beyond the 512-thread geometry (to 62 000 bases per sequence, windows to ~20 000 columns) run on the packed kernel's

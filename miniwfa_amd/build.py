@@ -9,8 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmwf_hip.so")
-SOURCES = ["mwf_kernels.hip", "mwf_band2.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
-HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
+SOURCES = ["mwf_kernels.hip", "mwf_band2.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_sys_deep.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
+HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
 
 
 def hipcc() -> str:
@@ -70,6 +70,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
 # which source file defines a kernel (by the start of its symbol): what a counter profile of that kernel is a profile OF
 KERNEL_FILES = {"wfa_band2_kernel": "mwf_band2.hip", "wfa_sys_kernel": "mwf_sys.hip", "wfa_sys_seg_kernel": "mwf_sys.hip", "wfa_batch_kernel": "mwf_kernels.hip",
                 "wfa_lane_kernel": "mwf_lane.hip", "wfa_mid_kernel": "mwf_mid.hip"}
+# further files that hold a source file's kernel code: the whole-device kernel's template lives in mwf_sys_pass.h and is instantiated by two units — a
+# wfa_sys_kernel<3,1,...> symbol comes from mwf_sys_deep.hip, and the prefix alone does not say which unit, so both are part of the fingerprint
+KERNEL_HEADERS = {"mwf_sys.hip": ["mwf_sys_pass.h", "mwf_sys_deep.hip"]}
 
 
 def kernel_fingerprint(symbol: str) -> str | None:
@@ -82,7 +85,7 @@ def kernel_fingerprint(symbol: str) -> str | None:
     if f is None:
         return None
     h = hashlib.sha256()
-    for p in (os.path.join(CSRC, f), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_internal.h")):
+    for p in [os.path.join(CSRC, x) for x in [f, *KERNEL_HEADERS.get(f, []), "mwf_device.h", "mwf_internal.h"]]:
         try:
             h.update(open(p, "rb").read())
         except OSError:

@@ -166,9 +166,14 @@ int64_t sys_chunk_slots(int grid);                   // chunk slots a launch of 
 int  sys_owned_cols(int p, int c);                   // columns a chunk slot owns: 64c - 2p
 bool sys_c_supported(int c);                         // columns per lane the build has kernels for (1 and 4; 2 only with -DMWF_SYS_C2)
 bool sys_p_supported(int p);                         // block lengths (penalties per hand-off) the build has kernels for
-int64_t sys_box_ints(int p, bool seg = false);                         // ints of one hand-off box
+// ints of one hand-off box: 2 (p/c) outer lanes x (p H rows + nef E/F arrays) c ints — whatever the columns per lane —, twice that with provenance, then the window views;
+// nef = 2 e1 + 2 e2 (sys_pass asserts that this is its BOX_INTS)
+constexpr int64_t sys_box_ints(int p, int nef, bool seg) { return ((seg ? 4 : 2) * p * (p + nef) + 2 * p + 31) / 32 * 32; }
+constexpr int64_t sys_park_ints(int nef, bool seg) { return (int64_t)(seg ? 2 : 1) * nef * 64 * 4; } // ints of a chunk slot's parked E/F registers (sized for four columns per lane)
+constexpr int kSysNotResident = -3;                  // launch_sys_pass(): the form it would launch does not fit a CU
 int  sys_max_grid();                                 // co-resident workgroups the kernel may be launched with (one per CU)
 int  launch_sys_pass(const BatchArgs &a, int grid, void *stream);        // forward pass (score / traceback bytes / second pass with band resets)
+int  launch_sys_pass_deep(const BatchArgs &a, int grid, void *stream);   // ... for gap extensions of 3 and 4 (mwf_sys_deep.hip; called by launch_sys_pass)
 int  launch_sys_walk(const BatchArgs &a, void *stream);
 int  launch_sys_trace(const BatchArgs &a, void *stream);                 // checkpoints from the snapshots of the systolic kernel's provenance pass                  // checkpoints from the traceback matrix of a first pass
 int  launch_sys_finish(const BatchArgs &a, void *stream);                // traceback + per-pair outputs

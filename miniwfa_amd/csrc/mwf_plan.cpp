@@ -531,7 +531,8 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	}
 
 	const int64_t sys_rows = std::max(bound, bound1) + 2, sys_log_ints = 2 * (sys_rows + 256 + 8), sys_ep_words = 2 * (sys_rows / 256 + 3);
-	const int64_t sys_box_group = TC * 2 * std::max(sys_box_ints(sysP, two_pass), sys_box_ints(sysP2, false)), sys_park_group = TC * (two_pass ? 16 : 8) * 64 * 4;
+	const int sys_nef = 2 * P.e1 + 2 * P.e2; // E/F register arrays per column: what a lane publishes and parks besides its H rows
+	const int64_t sys_box_group = TC * 2 * std::max(sys_box_ints(sysP, sys_nef, two_pass), sys_box_ints(sysP2, sys_nef, false)), sys_park_group = TC * sys_park_ints(sys_nef, two_pass);
 	if (use_sys) {
 		if (ensure(g, g->sys_ring, NG * (size_t)TC * P.nH * 256 * 4)) return -1;
 		if (ensure(g, g->sys_good, NG * (size_t)P.nH * TC * 4 * 8)) return -1;
@@ -607,7 +608,7 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	set_cols(c_first);
 	a.coop_pass = as.coop_pass = two_pass ? 3 : low_mem ? 1 : 0;
 	g->stats.lowmem_two_pass = two_pass ? 1 : 0;
-	if (launch_sys_pass(as, Gs * n_groups, g->stream)) { g->err = "kernel launch failed (whole-device pass)"; return -1; }
+	if (const int rc = launch_sys_pass(as, Gs * n_groups, g->stream)) { g->err = rc == kSysNotResident ? "whole-device kernel cannot be made resident" : "kernel launch failed (whole-device pass)"; return -1; }
 	g->stats.n_launches += 1;
 	if (low_mem) {
 		if (two_pass ? launch_sys_trace(as, g->stream) : launch_sys_walk(as, g->stream)) { g->err = "kernel launch failed (checkpoints)"; return -1; }
@@ -616,7 +617,7 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 		as.sys_p = sysP2;
 		set_cols(c_second);
 		// the second pass is not traced: the band trace of a low-memory run is that of its second pass, traced below
-		if (launch_sys_pass(as, Gs * n_groups, g->stream)) { g->err = "kernel launch failed (second pass)"; return -1; }
+		if (const int rc = launch_sys_pass(as, Gs * n_groups, g->stream)) { g->err = rc == kSysNotResident ? "whole-device kernel cannot be made resident" : "kernel launch failed (second pass)"; return -1; }
 		g->stats.n_launches += 2;
 	}
 	if (launch_sys_finish(as, g->stream)) { g->err = "kernel launch failed (traceback)"; return -1; }
