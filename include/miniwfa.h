@@ -63,7 +63,8 @@ void mwf_opt_init(mwf_opt_t *opt);
  * Every penalty set gives the reference's answer; which kernels serve it depends on the gap extensions (e1, e2): the whole-device kernel for
  * long pairs ("coop_min_len" below) takes (2,1), (2,2), (1,1) and e1 in {3, 4} with e2 in {1, 2} (minimap2's asm5 / asm20-like sets); under any
  * other pair of extensions long pairs run on the generic one-workgroup-per-pair kernel (about ten times slower on a 150 kb pair).  The packed
- * band kernel for big batches of mid-size pairs takes (2,1), (2,2), (1,1) only; other sets run such batches on the generic kernel.
+ * band kernel for big batches of mid-size pairs takes (2,1), (2,2), (1,1) and (3,1), (3,2), (4,1); under any other pair of extensions — (4,2)
+ * among them, which was measured and gained too little — such batches run on the generic kernel (1.3 to 2.2 times slower on 1024 x 10 kb).
  * Device: MWF_DEVICE=<ordinal> (default 0).  Any number of host threads may call concurrently. */
 void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r);
 

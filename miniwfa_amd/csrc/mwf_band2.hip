@@ -312,7 +312,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	// (PairMem::tb_fwd), and the walk reads them from the cell an extension would come from (traceback_wave: one more byte per gap run).
 	constexpr int kAgeOut = FOLD ? kFoldMaxLag : D;
 	constexpr int kAge = (NWK + 2) * 16; // bytes of one age of the edge table
-	static_assert(D == 2 || D == 3, "edge-table ages");
+	static_assert(D >= 2 && D <= 5, "edge-table ages"); // one table per penalty an E/F can be read back from, plus the one being written: epos[] rotates through them
 	const int32_t tl = M.tl, ql = M.ql, cmax = tl + ql + 1;
 	const int32_t tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
 	const int32_t W = A.W, nH = A.pen.nH, lagx = A.pen.x, lag1 = A.pen.oe1, lag2 = A.pen.oe2;
@@ -328,7 +328,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	R.status = ST_OK, R.s = 0, R.info = 0, R.n_snap = 0, R.cells = 0;
 
 	// per-thread wavefront state, two columns per register: [age - 1][slot][A / B]
-	static_assert((E1 == 1 || E1 == 2) && (E2 == 1 || E2 == 2), "history depth");
+	static_assert(E1 >= 1 && E1 <= 4 && (E2 == 1 || E2 == 2), "history depth");
 	int32_t e1h[E1][K][2], f1h[E1][K][2], e2h[E2][K][2], f2h[E2][K][2];
 #pragma unroll
 	for (int k = 0; k < K; ++k)
@@ -425,6 +425,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 
 	// One penalty; returns true when the pass ends.  A depth-2 history is two registers, [0] the newer: the penalty reads [1] for the last
 	// time, overwrites it, and the two trade places (v_swap_b32) — no copies, and a slot that is skipped leaves its registers alone.
+	// Depth 3 and 4 (gap extensions of 3 and 4): the penalty reads and overwrites the oldest, [E - 1], and the new value trades places with
+	// its neighbour E - 1 times on its way to [0] — a rotation by one, every other age one place older.
 	auto step = [&]() __attribute__((always_inline)) -> bool {
 		constexpr int P1 = E1 - 1, P2 = E2 - 1;
 #ifdef MWF_B2_TIMING
@@ -666,13 +668,15 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			e2h[P2][k][0] = ne2A, e2h[P2][k][1] = ne2B, f2h[P2][k][0] = nf2A, f2h[P2][k][1] = nf2B;
 #pragma unroll
 			for (int i = 0; i < 2; ++i) {
-				if (E1 == 2) {
-					asm volatile("v_swap_b32 %0, %1" : "+v"(e1h[0][k][i]), "+v"(e1h[1][k][i]));
-					asm volatile("v_swap_b32 %0, %1" : "+v"(f1h[0][k][i]), "+v"(f1h[1][k][i]));
+#pragma unroll
+				for (int a = E1 - 1; a > 0; --a) {
+					asm volatile("v_swap_b32 %0, %1" : "+v"(e1h[a - 1][k][i]), "+v"(e1h[a][k][i]));
+					asm volatile("v_swap_b32 %0, %1" : "+v"(f1h[a - 1][k][i]), "+v"(f1h[a][k][i]));
 				}
-				if (E2 == 2) {
-					asm volatile("v_swap_b32 %0, %1" : "+v"(e2h[0][k][i]), "+v"(e2h[1][k][i]));
-					asm volatile("v_swap_b32 %0, %1" : "+v"(f2h[0][k][i]), "+v"(f2h[1][k][i]));
+#pragma unroll
+				for (int a = E2 - 1; a > 0; --a) {
+					asm volatile("v_swap_b32 %0, %1" : "+v"(e2h[a - 1][k][i]), "+v"(e2h[a][k][i]));
+					asm volatile("v_swap_b32 %0, %1" : "+v"(f2h[a - 1][k][i]), "+v"(f2h[a][k][i]));
 				}
 			}
 			put_edge(k, ne1B, ne2B, nf1A, nf2A);
@@ -918,8 +922,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 
 // Workgroups share a CU: 2 x 512, 4 x 256, 8 x 128 or 16 x 64 threads = 4 waves per SIMD, i.e. at most 128 VGPRs; with traceback
 // the smaller ones get 168 (3 per SIMD).  768 threads: one workgroup per CU.
+// (gap extensions of 3 and 4 keep these bounds: profiles/band_deep/band2_deep_registers.txt has what that spills, DESIGN.md section 4.2 what was measured)
+constexpr int band2_waves(int T, int K, bool TB)
+{
+	return is_span(T, K) ? (T == 1024 ? 4 : 3) : T == 1024 ? 4 : T == kWideT ? kWideWaves : T <= 512 ? ((TB && T < 512) ? 3 : 4) : kWaves768;
+}
 template <int T, int K, int E1, int E2, bool TB, bool S2, bool BI4 = false, bool FOLD = false>
-__global__ __launch_bounds__(T, is_span(T, K) ? (T == 1024 ? 4 : 3) : T == 1024 ? 4 : T == kWideT ? kWideWaves : T <= 512 ? ((TB && T < 512) ? 3 : 4) : kWaves768) void wfa_band2_kernel(const BatchArgs)
+__global__ __launch_bounds__(T, band2_waves(T, K, TB)) void wfa_band2_kernel(const BatchArgs)
 {
 	constexpr int NWK = (T / 64) * K, D = (E1 > E2 ? E1 : E2) + 1;
 	// the arguments are read from the kernarg segment where they are used (dev::kernel_args / dev::fresh), never held for the kernel's lifetime
@@ -1042,11 +1051,26 @@ int occ_one(int lds_seq, bool seq2, bool tb)
 
 } // namespace
 
+// Gap extensions of 3 and 4 — (e1, e2) = (3,1), (3,2), (4,1), minimap2's asm5 / asm20-like sets — are instantiated by two units of their own, mwf_band2_e3.hip and
+// mwf_band2_e4.hip, which include this file with MWF_BAND2_DEEP set to their e1: they compile beside this one, each holds the template above and, of what
+// follows, only its own dispatch (launch_band2_e3 / _e4, band2_occupancy_e3 / _e4), on every geometry but the 512 x 5 / 512 x 6 copies on biased offsets, never folded.
+// (4,2) is not built: its 10 kb batches run on the span geometry (e2 == 2: the worst-case penalty does not fit plain 16-bit offsets), where 24 history registers
+// per slot spill ~100 VGPRs, and gained 1.17 x / 1.13 x over the generic kernel — below what its code is worth.
+#define MWF_BAND2_CAT_(a, b) a##b
+#define MWF_BAND2_CAT(a, b) MWF_BAND2_CAT_(a, b)
+int launch_band2_e3(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int launch_band2_e4(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int band2_occupancy_e3(const Penalty &p, const BandGeom &g, bool cigar);
+int band2_occupancy_e4(const Penalty &p, const BandGeom &g, bool cigar);
+
+#ifndef MWF_BAND2_DEEP
 // the packed kernel: (e1,e2) instantiated, sequences fit LDS (the host checks), every H lag >= 1
 bool band2_supported(const Penalty &p)
 {
-	return ((p.e1 == 2 && p.e2 == 1) || (p.e1 == 2 && p.e2 == 2) || (p.e1 == 1 && p.e2 == 1)) && p.nH <= kMaxRing; // (window table in LDS; rows read as dead up to 256 columns beyond their window)
+	const bool deep = (p.e1 == 3 && (p.e2 == 1 || p.e2 == 2)) || (p.e1 == 4 && p.e2 == 1);
+	return ((p.e1 == 2 && p.e2 == 1) || (p.e1 == 2 && p.e2 == 2) || (p.e1 == 1 && p.e2 == 1) || deep) && p.nH <= kMaxRing; // (window table in LDS; rows read as dead up to 256 columns beyond their window)
 }
+#endif
 
 #ifdef MWF_BAND_DEV
 #define MWF_BAND2_REST(FN, ...)
@@ -1056,7 +1080,18 @@ bool band2_supported(const Penalty &p)
 	if (g.block == 128) MWF_BAND2_PEN(FN, 128, 3, __VA_ARGS__)                      \
 	if (g.block == 64) MWF_BAND2_PEN(FN, 64, 3, __VA_ARGS__)
 #endif
-#ifdef MWF_BAND_DEV
+#if defined(MWF_BAND2_DEEP) && MWF_BAND2_DEEP == 3
+#define MWF_BAND2_PEN(FN, T, K, ...)                                                \
+	{                                                                               \
+		if (a_e1 == 3 && a_e2 == 1) return FN<T, K, 3, 1>(__VA_ARGS__);             \
+		if (a_e1 == 3 && a_e2 == 2) return FN<T, K, 3, 2>(__VA_ARGS__);             \
+	}
+#elif defined(MWF_BAND2_DEEP) /* e1 = 4: (4,1) alone — an arm that cannot run would still instantiate its kernels */ 
+#define MWF_BAND2_PEN(FN, T, K, ...)                                                \
+	{                                                                               \
+		if (a_e1 == MWF_BAND2_DEEP && a_e2 == 1) return FN<T, K, MWF_BAND2_DEEP, 1>(__VA_ARGS__); \
+	}
+#elif defined(MWF_BAND_DEV)
 #define MWF_BAND2_PEN(FN, T, K, ...) { if (a_e1 == 2 && a_e2 == 1) return FN<T, K, 2, 1>(__VA_ARGS__); }
 #else
 #define MWF_BAND2_PEN(FN, T, K, ...)                                                \
@@ -1067,6 +1102,10 @@ bool band2_supported(const Penalty &p)
 	}
 #endif
 /* (the five / six-slot copies on biased offsets: gap extensions (2, 1) only — band2_biased512_supported; other penalty sets take the span geometry) */
+#ifdef MWF_BAND2_DEEP
+#define MWF_BAND2_PEN4B(FN, ...) {}
+#define MWF_BAND2_PEN4C(FN, ...) {}
+#else
 #define MWF_BAND2_PEN4B(FN, ...)                                                    \
 	{                                                                               \
 		if (a_e1 == 2 && a_e2 == 1) return FN<512, kW4K, 2, 1, true>(__VA_ARGS__);     \
@@ -1075,6 +1114,7 @@ bool band2_supported(const Penalty &p)
 	{                                                                               \
 		if (a_e1 == 2 && a_e2 == 1) return FN<512, kW4K + 1, 2, 1, true>(__VA_ARGS__); \
 	}
+#endif
 #define MWF_BAND2_DISPATCH(FN, ...)                                                 \
 	do {                                                                            \
 		if (g.block == 512 && g.span > 8 * kW4K * 256 && g.packed == 2) MWF_BAND2_PEN4C(FN, __VA_ARGS__) /* ... six slots on biased offsets (pairs of up to ~21 kb) */ \
@@ -1086,9 +1126,28 @@ bool band2_supported(const Penalty &p)
 		MWF_BAND2_REST(FN, __VA_ARGS__)                                             \
 	} while (0)
 
+#ifdef MWF_BAND2_DEEP
+int MWF_BAND2_CAT(launch_band2_e, MWF_BAND2_DEEP)(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
+{
+	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
+	if (g.packed == 2) return -1; // (no copies of the 512-thread geometry on biased offsets for these sets)
+	MWF_BAND2_DISPATCH(launch_one, a, grid, g.lds_bytes, g.seq2 != 0, (hipStream_t)stream);
+	return -1;
+}
+
+int MWF_BAND2_CAT(band2_occupancy_e, MWF_BAND2_DEEP)(const Penalty &p, const BandGeom &g, bool cigar)
+{
+	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (g.packed == 2) return 0;
+	MWF_BAND2_DISPATCH(occ_one, g.lds_bytes, g.seq2 != 0, cigar);
+	return 0;
+}
+#else
 int launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
+	if (a_e1 == 3) return launch_band2_e3(a, grid, g, stream);
+	if (a_e1 == 4) return launch_band2_e4(a, grid, g, stream);
 	MWF_BAND2_DISPATCH(launch_one, a, grid, g.lds_bytes, g.seq2 != 0, (hipStream_t)stream);
 	return -1;
 }
@@ -1100,8 +1159,11 @@ bool band2_biased512_supported(const Penalty &p) { return p.e1 == 2 && p.e2 == 1
 int band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar)
 {
 	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (a_e1 == 3) return band2_occupancy_e3(p, g, cigar);
+	if (a_e1 == 4) return band2_occupancy_e4(p, g, cigar);
 	MWF_BAND2_DISPATCH(occ_one, g.lds_bytes, g.seq2 != 0, cigar);
 	return 0;
 }
+#endif
 
 } // namespace mwf
