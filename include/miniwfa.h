@@ -65,6 +65,8 @@ void mwf_opt_init(mwf_opt_t *opt);
  * other pair of extensions long pairs run on the generic one-workgroup-per-pair kernel (about ten times slower on a 150 kb pair).  The packed
  * band kernel for big batches of mid-size pairs takes (2,1), (2,2), (1,1) and (3,1), (3,2), (4,1); under any other pair of extensions — (4,2)
  * among them, which was measured and gained too little — such batches run on the generic kernel (1.3 to 2.2 times slower on 1024 x 10 kb).
+ * Under each of those six sets, pairs too long for plain 16-bit offsets (from ~6.6 kb where e2 == 2 — the -a preset's 10 kb batches —, from ~11 kb
+ * where e2 == 1, up to ~21 kb) keep two workgroups per CU on that kernel's 512-thread copies on biased offsets.
  * Device: MWF_DEVICE=<ordinal> (default 0).  Any number of host threads may call concurrently. */
 void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r);
 

@@ -40,7 +40,8 @@ constexpr int kSpanK = 5;
 // Chunk slots per wave of the 512-thread geometry's copies on biased offsets (class 14 of mwf_plan.cpp: pairs of ~11-21 kb, two per CU instead of the span
 // geometry's one).  Measured (ms per align; span geometry | 4 | 5 | 6 slots): 1024 x 12 kb @ 5 % 34.9 | 24.6 | 24.8 | 27.7, 1024 x 15 kb @ 4 % 35.6 | - | 25.1 | 25.7,
 // 1024 x 17 kb @ 3 % 29.5 | - | 20.2 | 20.5, 512 x 18 kb @ 5 % 32.1 | - | - | 25.3, 1024 x 20 kb @ 3 % 37.3 | - | - | 26.9: five slots (40 chunks, 4 spilled VGPRs)
-// while target + query stay below 3.5 of their span, six (48 chunks) up to 3.5 of theirs.
+// while target + query stay below 3.5 of their span, six (48 chunks) up to 3.5 of theirs.  (Those are the default set's figures.  The other sets' copies — same slot
+// counts, mwf_band2_bi.hip / mwf_band2_bi_deep.hip — against the span geometry: DESIGN.md section 4.2, profiles/band_biased/.)
 constexpr int kW4K = 5;
 constexpr int kSpanT = 1024;  // threads of the span geometry (measured: 768 x 7 slots — twelve waves, 168 VGPRs, no spills — 187.6 against 178.7 ms on 1250 x 50 kb, 768 x 6 189.6)
 constexpr bool is_span(int T, int K) { return T == kSpanT && K == kSpanK; }
@@ -922,7 +923,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 
 // Workgroups share a CU: 2 x 512, 4 x 256, 8 x 128 or 16 x 64 threads = 4 waves per SIMD, i.e. at most 128 VGPRs; with traceback
 // the smaller ones get 168 (3 per SIMD).  768 threads: one workgroup per CU.
-// (gap extensions of 3 and 4 keep these bounds: profiles/band_deep/band2_deep_registers.txt has what that spills, DESIGN.md section 4.2 what was measured)
+// (gap extensions of 3 and 4 keep these bounds: profiles/band_deep/band2_deep_registers.txt has what that spills, DESIGN.md section 4.2 what was measured;
+// likewise the five / six-slot copies on biased offsets of the sets beyond (2,1): profiles/band_biased/band2_biased_registers.txt)
 constexpr int band2_waves(int T, int K, bool TB)
 {
 	return is_span(T, K) ? (T == 1024 ? 4 : 3) : T == 1024 ? 4 : T == kWideT ? kWideWaves : T <= 512 ? ((TB && T < 512) ? 3 : 4) : kWaves768;
@@ -1054,6 +1056,9 @@ int occ_one(int lds_seq, bool seq2, bool tb)
 // Gap extensions of 3 and 4 — (e1, e2) = (3,1), (3,2), (4,1), minimap2's asm5 / asm20-like sets — are instantiated by two units of their own, mwf_band2_e3.hip and
 // mwf_band2_e4.hip, which include this file with MWF_BAND2_DEEP set to their e1: they compile beside this one, each holds the template above and, of what
 // follows, only its own dispatch (launch_band2_e3 / _e4, band2_occupancy_e3 / _e4), on every geometry but the 512 x 5 / 512 x 6 copies on biased offsets, never folded.
+// Those copies (class 14 of mwf_plan.cpp) for every set but (2, 1) live in two further units, mwf_band2_bi.hip — (2,2), folded and not, and (1,1) — and
+// mwf_band2_bi_deep.hip — (3,1), (3,2), (4,1) —, which include this file with MWF_BAND2_BIASED set to 1 / 2 and hold launch_band2_bi1 / _bi2, band2_occupancy_bi1 / _bi2
+// and nothing else; (2, 1)'s stay in this unit.
 // (4,2) is not built: its 10 kb batches run on the span geometry (e2 == 2: the worst-case penalty does not fit plain 16-bit offsets), where 24 history registers
 // per slot spill ~100 VGPRs, and gained 1.17 x / 1.13 x over the generic kernel — below what its code is worth.
 #define MWF_BAND2_CAT_(a, b) a##b
@@ -1062,8 +1067,12 @@ int launch_band2_e3(const BatchArgs &a, int grid, const BandGeom &g, void *strea
 int launch_band2_e4(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int band2_occupancy_e3(const Penalty &p, const BandGeom &g, bool cigar);
 int band2_occupancy_e4(const Penalty &p, const BandGeom &g, bool cigar);
+int launch_band2_bi1(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int launch_band2_bi2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int band2_occupancy_bi1(const Penalty &p, const BandGeom &g, bool cigar);
+int band2_occupancy_bi2(const Penalty &p, const BandGeom &g, bool cigar);
 
-#ifndef MWF_BAND2_DEEP
+#if !defined(MWF_BAND2_DEEP) && !defined(MWF_BAND2_BIASED)
 // the packed kernel: (e1,e2) instantiated, sequences fit LDS (the host checks), every H lag >= 1
 bool band2_supported(const Penalty &p)
 {
@@ -1072,7 +1081,7 @@ bool band2_supported(const Penalty &p)
 }
 #endif
 
-#ifdef MWF_BAND_DEV
+#if defined(MWF_BAND_DEV) || defined(MWF_BAND2_BIASED)
 #define MWF_BAND2_REST(FN, ...)
 #else
 #define MWF_BAND2_REST(FN, ...)                                                     \
@@ -1080,7 +1089,9 @@ bool band2_supported(const Penalty &p)
 	if (g.block == 128) MWF_BAND2_PEN(FN, 128, 3, __VA_ARGS__)                      \
 	if (g.block == 64) MWF_BAND2_PEN(FN, 64, 3, __VA_ARGS__)
 #endif
-#if defined(MWF_BAND2_DEEP) && MWF_BAND2_DEEP == 3
+#if defined(MWF_BAND2_BIASED) /* the copies on biased offsets alone: no other geometry */
+#define MWF_BAND2_PEN(FN, T, K, ...) {}
+#elif defined(MWF_BAND2_DEEP) && MWF_BAND2_DEEP == 3
 #define MWF_BAND2_PEN(FN, T, K, ...)                                                \
 	{                                                                               \
 		if (a_e1 == 3 && a_e2 == 1) return FN<T, K, 3, 1>(__VA_ARGS__);             \
@@ -1101,8 +1112,25 @@ bool band2_supported(const Penalty &p)
 		if (a_e1 == 1 && a_e2 == 1) return FN<T, K, 1, 1>(__VA_ARGS__);             \
 	}
 #endif
-/* (the five / six-slot copies on biased offsets: gap extensions (2, 1) only — band2_biased512_supported; other penalty sets take the span geometry) */
-#ifdef MWF_BAND2_DEEP
+/* (the five / six-slot copies on biased offsets: (2, 1) here, the other sets in mwf_band2_bi.hip / mwf_band2_bi_deep.hip — band2_biased512_supported) */
+#if defined(MWF_BAND2_BIASED) && MWF_BAND2_BIASED == 1
+#define MWF_BAND2_PEN4(FN, K, ...)                                                  \
+	{                                                                               \
+		if (a_e1 == 2 && a_e2 == 2) return FN<512, K, 2, 2, true>(__VA_ARGS__);     \
+		if (a_e1 == 1 && a_e2 == 1) return FN<512, K, 1, 1, true>(__VA_ARGS__);     \
+	}
+#elif defined(MWF_BAND2_BIASED)
+#define MWF_BAND2_PEN4(FN, K, ...)                                                  \
+	{                                                                               \
+		if (a_e1 == 3 && a_e2 == 1) return FN<512, K, 3, 1, true>(__VA_ARGS__);     \
+		if (a_e1 == 3 && a_e2 == 2) return FN<512, K, 3, 2, true>(__VA_ARGS__);     \
+		if (a_e1 == 4 && a_e2 == 1) return FN<512, K, 4, 1, true>(__VA_ARGS__);     \
+	}
+#endif
+#if defined(MWF_BAND2_BIASED)
+#define MWF_BAND2_PEN4B(FN, ...) MWF_BAND2_PEN4(FN, kW4K, __VA_ARGS__)
+#define MWF_BAND2_PEN4C(FN, ...) MWF_BAND2_PEN4(FN, kW4K + 1, __VA_ARGS__)
+#elif defined(MWF_BAND2_DEEP)
 #define MWF_BAND2_PEN4B(FN, ...) {}
 #define MWF_BAND2_PEN4C(FN, ...) {}
 #else
@@ -1126,7 +1154,23 @@ bool band2_supported(const Penalty &p)
 		MWF_BAND2_REST(FN, __VA_ARGS__)                                             \
 	} while (0)
 
-#ifdef MWF_BAND2_DEEP
+#if defined(MWF_BAND2_BIASED)
+int MWF_BAND2_CAT(launch_band2_bi, MWF_BAND2_BIASED)(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
+{
+	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
+	if (g.packed != 2) return -1; // (this unit holds the copies on biased offsets and nothing else)
+	MWF_BAND2_DISPATCH(launch_one, a, grid, g.lds_bytes, g.seq2 != 0, (hipStream_t)stream);
+	return -1;
+}
+
+int MWF_BAND2_CAT(band2_occupancy_bi, MWF_BAND2_BIASED)(const Penalty &p, const BandGeom &g, bool cigar)
+{
+	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (g.packed != 2) return 0;
+	MWF_BAND2_DISPATCH(occ_one, g.lds_bytes, g.seq2 != 0, cigar);
+	return 0;
+}
+#elif defined(MWF_BAND2_DEEP)
 int MWF_BAND2_CAT(launch_band2_e, MWF_BAND2_DEEP)(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
@@ -1146,6 +1190,7 @@ int MWF_BAND2_CAT(band2_occupancy_e, MWF_BAND2_DEEP)(const Penalty &p, const Ban
 int launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
+	if (g.packed == 2 && !(a_e1 == 2 && a_e2 == 1)) return a_e1 <= 2 ? launch_band2_bi1(a, grid, g, stream) : launch_band2_bi2(a, grid, g, stream);
 	if (a_e1 == 3) return launch_band2_e3(a, grid, g, stream);
 	if (a_e1 == 4) return launch_band2_e4(a, grid, g, stream);
 	MWF_BAND2_DISPATCH(launch_one, a, grid, g.lds_bytes, g.seq2 != 0, (hipStream_t)stream);
@@ -1154,11 +1199,16 @@ int launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 
 int band2_span_chunks() { return kSpanT / 64 * kSpanK; }
 int band2_biased512_chunks() { return 8 * kW4K; }
-bool band2_biased512_supported(const Penalty &p) { return p.e1 == 2 && p.e2 == 1; }
+// (the sets whose copies are built: (2,1) in this unit, the others in mwf_band2_bi.hip / mwf_band2_bi_deep.hip; (4,2) is not on this kernel at all)
+bool band2_biased512_supported(const Penalty &p)
+{
+	return (p.e1 == 2 && (p.e2 == 1 || p.e2 == 2)) || (p.e1 == 1 && p.e2 == 1) || (p.e1 == 3 && (p.e2 == 1 || p.e2 == 2)) || (p.e1 == 4 && p.e2 == 1);
+}
 
 int band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar)
 {
 	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (g.packed == 2 && !(a_e1 == 2 && a_e2 == 1)) return a_e1 <= 2 ? band2_occupancy_bi1(p, g, cigar) : band2_occupancy_bi2(p, g, cigar);
 	if (a_e1 == 3) return band2_occupancy_e3(p, g, cigar);
 	if (a_e1 == 4) return band2_occupancy_e4(p, g, cigar);
 	MWF_BAND2_DISPATCH(occ_one, g.lds_bytes, g.seq2 != 0, cigar);

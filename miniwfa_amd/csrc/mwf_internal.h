@@ -151,7 +151,7 @@ int  batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool r
 // geometry of a launch of the band family (mwf_band2.hip packed band kernel, mwf_lane.hip, mwf_mid.hip)
 struct BandGeom {
 	int block;        // threads per workgroup: 256 (x2 chunks), 768 (x2 chunks) or 512 (x3 chunks, packed state)
-	int packed;       // 1: the packed band kernel (mwf_band2.hip: E/F register state as int16 pairs, 16-bit H rows); 2: its 512 x 4 geometry's copy on biased offsets
+	int packed;       // 1: the packed band kernel (mwf_band2.hip: E/F register state as int16 pairs, 16-bit H rows); 2: its 512-thread geometry's five / six-slot copies on biased offsets
 	int span;         // columns the workgroup can hold: waves * chunks * 256 (balanced kernel: columns of its LDS state ring)
 	int lds_bytes;    // dynamic LDS for the sequence copy (0: read sequences from global memory)
 	int seq2;         // packed kernel: the sequence copy holds 2 bits per base (pairs of plain A/C/G/T; others come back as ST_ALPHABET)
@@ -193,7 +193,7 @@ int  launch_mid(const BatchArgs &a, int grid, int block, int lds, bool seq2, voi
 bool band2_supported(const Penalty &p);
 int  launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar);
-bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for gap extensions (2, 1) only
+bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for the set: every set band2_supported takes
 int  band2_biased512_chunks();                       // ... and the 512-thread geometry's copy on biased offsets (8 waves x slots per wave)
 int  band2_span_chunks();                            // 256-column chunks its 1024-thread geometry holds (16 waves x slots per wave)
 

@@ -59,9 +59,11 @@ struct Plan {
 	bool low_mem = false, cigar = false;
 };
 
+int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16 = false);
+
 // Which kernel serves a set of pairs.  The band kernel keeps E/F in registers and therefore only holds windows up to
 // its span; it has no low-memory first pass.  kind: -1 automatic, 0 generic, 2 band.
-void choose_kernel(const mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t max_len, int64_t max_bound,
+void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t max_len, int64_t max_bound,
                    int64_t max_seq_lds, int64_t max_tl, int want_kind, Plan &pl, int geom_block = 0, int64_t window_hint = 0)
 {
 	pl.kind = 0;
@@ -100,7 +102,7 @@ void choose_kernel(const mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, i
 		}
 	}
 	if (want_kind == 0 || low_mem || !can_packed) return;
-	if (geom_block == 514) { // the 512-thread geometry with four chunk slots on biased offsets (the caller checked the lengths: kBandSpanMaxSeq); 2-bit copies only
+	if (geom_block == 514) { // the 512-thread geometry with five / six chunk slots on biased offsets (the caller checked the lengths: kBandSpanMaxSeq); 2-bit copies only
 		const int64_t need_lds = ((max_len >> 4) + 4) * 4;
 		if (g->seq2bit == 0 || g->acgt_off_once || need_lds > 70 * 1024 || !band2_biased512_supported(P)) return;
 		// (five chunk slots per wave while target + query stay below 3.5 of that span, else six)
@@ -109,7 +111,12 @@ void choose_kernel(const mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, i
 		const bool six = max_len + 1 > 7 * (int64_t)(band2_biased512_chunks() * 256) / 2 || (window_hint > 0 && window_hint + 768 > ((int64_t)band2_biased512_chunks() - 1) * 256 - 64);
 		const int chunks = band2_biased512_chunks() + (six ? 8 : 0);
 		pl.kind = 2, pl.band = BandGeom{512, 2, chunks * 256, (int)((need_lds + 15) / 16 * 16), 1, 0}; // (packed 2: the copy that computes on biased offsets)
-		return;
+		// The geometry is worth its registers only two to a CU.  The launch adds the set's own edge table to the sequence copy — max(e1, e2) + 1 ages of
+		// chunks + 2 entries, 2.0 KB for (2,1) on five slots, 3.9 KB for (4,1) on six — so the kernel is asked, with this class's longest pair in LDS:
+		// fewer than two resident workgroups, and the pairs take the span geometry as they would without these copies.
+		pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
+		if (cached_occupancy(g, P, pl, 0, false) >= 2) return;
+		pl.kind = 0, pl.band = BandGeom{0, 0, 0, 0, 0, 0}, geom_block = 1024;
 	}
 	if (geom_block == 1024) { // the span geometry (the caller checked the lengths of every pair: kBandSpanMaxSeq); 2-bit sequence copies only
 		const int64_t need_lds = ((max_len >> 4) + 4) * 4;
@@ -170,7 +177,7 @@ void choose_kernel(const mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, i
 }
 
 // resident workgroups per CU of a kernel variant (one runtime query per variant and engine)
-int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16 = false)
+int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16)
 {
 	uint64_t key;
 	if (pl.kind == 2)
@@ -792,8 +799,9 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	// (12: the pairs of class 10 the host knows not to be plain A/C/G/T — reads with an N —: the lane kernel on byte-wise copies)
 	// 13: pairs too long (or with windows too wide) for the 512-thread packed geometry on its 1024-thread span geometry: targets of up to ~60 kb on biased
 	// 16-bit offsets, windows of up to ~16 000 columns; what outgrows it moves to the generic kernel
-	// 14: pairs of up to ~16 kb per sequence whose worst-case penalty rules out plain 16-bit offsets: the 512-thread geometry with four chunk slots, which computes on
-	// biased offsets with range checks like the span geometry but keeps two pairs per CU (windows of up to 7872 columns; what outgrows them moves to the span geometry)
+	// 14: pairs of up to ~21 kb per sequence whose worst-case penalty rules out plain 16-bit offsets: the 512-thread geometry with five or six chunk slots, which computes on
+	// biased offsets with range checks like the span geometry but keeps two pairs per CU (windows of up to 9920 / 11 968 columns; what outgrows them moves to the span geometry).
+	// Built for every set the band kernel takes (band2_biased512_supported): where e2 == 2 — main.c's -a preset — the class starts at ~6.6 kb, 1024 x 10 kb batches are its.
 	static const int run_order[15] = {5, 0, 13, 14, 1, 6, 2, 7, 3, 8, 4, 9, 11, 10, 12}; // largest workspace first
 	if (PC.has_groups) { // same lengths, same options, same tunables as last time: classes, order (already on the device) and maxima as they were
 		b->h_class = PC.cls0, b->h_flags = PC.flags0;
