@@ -24,6 +24,10 @@
 // A pair whose window leaves the chunks, or that reaches the first shrink (penalty 256 - nH), comes back as ST_BAND_OVERFLOW and is
 // re-run on the packed band kernel (finalize(), mwf_plan.cpp).  Reference: wf_next_basic + wf_extend + the loop of mwf_wfa_core
 // (miniwfa.c:252-326, :380-430).
+// Rule: an instantiation of wfa_lane_kernel<TB, S2, FOLD> is added (or removed) together with its entry in tests/lane_mid_matrix.py
+// (tests/test_lane_mid_cpu.py compares the table with the built object; tests/test_lane_mid_matrix_gpu.py runs one test per entry).
+#include <cstdio>
+#include <cstdlib>
 #include "mwf_device.h"
 
 namespace mwf {
@@ -255,6 +259,9 @@ int launch_lane(const BatchArgs &a, int grid, int lds, bool seq2, void *stream)
 		(void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 		(void)hipGetLastError();
 	}
+	// diagnostics: which instantiation this launch is — the three template arguments, as tests/lane_mid_matrix.py lists them — and how many pairs it was given
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] lane launch: TB %d S2 %d FOLD %d, chunks %d, %d pairs, grid %d\n", (int)(a.want_cigar != 0), (int)seq2, (int)fold, (int)a.lane_chunks, (int)a.n_pairs, grid);
 	if (a.want_cigar) {
 		if (seq2) hipLaunchKernelGGL((wfa_lane_kernel<true, true>), dim3(grid), dim3(64), lds, (hipStream_t)stream, a);
 		else hipLaunchKernelGGL((wfa_lane_kernel<true, false>), dim3(grid), dim3(64), lds, (hipStream_t)stream, a);

@@ -24,6 +24,10 @@
 //     (mwf_device.h) finds a byte without reading a row table first.
 // A pair whose window leaves the span comes back as ST_BAND_OVERFLOW and is re-run on the packed band kernel (finalize()).
 // Results are bit-identical to every other kernel (tests/test_gpu_parity.py::test_mid_kernel_*).
+// Rule: an instantiation of wfa_mid_kernel<T, TB, S2, FOLD> is added (or removed) together with its entry in tests/lane_mid_matrix.py
+// (tests/test_lane_mid_cpu.py compares the table with the built object; tests/test_lane_mid_matrix_gpu.py runs one test per entry).
+#include <cstdio>
+#include <cstdlib>
 #include "mwf_device.h"
 
 namespace mwf {
@@ -327,6 +331,9 @@ int launch_v(const BatchArgs &a, int grid, int lds, hipStream_t st)
 		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wfa_mid_kernel<T, TB, S2, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 		(void)hipGetLastError();
 	}
+	// diagnostics: which instantiation this launch is — the four template arguments, as tests/lane_mid_matrix.py lists them — and how many pairs it was given
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] mid launch: T %d TB %d S2 %d FOLD %d, groups %d, %d pairs, grid %d\n", T, (int)TB, (int)S2, (int)FOLD, (int)a.lane_chunks, (int)a.n_pairs, grid);
 	hipLaunchKernelGGL((wfa_mid_kernel<T, TB, S2, FOLD>), dim3(grid), dim3(T), lds, st, a);
 	return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -855,8 +855,11 @@ def test_lane_kernel_short_pairs_fuzz_against_oracle(chunks, oracle):
             assert (int(s[i]), int(it[i])) == (es, eit), (chunks, kw, i, len(t), len(q))
             if ecig is not None and es >= 0:
                 assert b.cigar(i, int(nc[i])).tolist() == ecig, (chunks, kw, i)
+        s, it = np.array(s).copy(), np.array(it).copy()
         b.free()
         eng.close()
+        if "max_s" not in kw:
+            _check_hand_backs(oracle, pk, pairs, kw, s, it, (("lane_chunks", chunks),), dict(lane_chunks=chunks))
     eng = mw.Engine(0)
     eng.set("lane_max_len", 0)  # switched off (and the mid kernel, which takes the pairs of a batch this small, as well): the band kernels take the short pairs
     eng.set("mid_max_pairs", 0)
@@ -894,8 +897,32 @@ def test_mid_kernel_fuzz_against_oracle(oracle):
             assert (int(s[i]), int(it[i])) == (es, eit), (block, kw, i, len(t), len(q))
             if ecig is not None and es >= 0:
                 assert b.cigar(i, int(nc[i])).tolist() == ecig, (block, kw, i)
+        s, it = np.array(s).copy(), np.array(it).copy()
         b.free()
         eng.close()
+        if "max_s" not in kw and "max_iter" not in kw:
+            _check_hand_backs(oracle, pk, pairs, kw, s, it, (("mid_block", block), ("seq2bit", s2)), dict())
+
+
+def _check_hand_backs(oracle, pk, pairs, kw, s, it, tunables, rule_kw):
+    """The same align once more with the classes drawn from the lengths alone ("div_aware" 0): the lane and the mid kernel finish what the rules restated in
+    tests/lane_mid_matrix.py say they must — the re-runs stay within the pairs those rules let a kernel hand back (may_hand_back) — and the answers are the same."""
+    import lane_mid_matrix as lm
+    import torch
+    if len(pairs) > torch.cuda.get_device_properties(0).multi_processor_count:   # (the rules are those of a batch small enough for the mid kernel)
+        return
+    may = lm.may_hand_back(oracle, pairs, kw, **rule_kw)
+    eng = mw.Engine(0)
+    for k, v in tunables + (("div_aware", 0),):
+        eng.set(k, v)
+    b = eng.upload(pk)
+    b.align(mw.opt_init(**kw))
+    s2, it2, _ = b.results()
+    n = int(eng.stats().n_retries)
+    assert (np.array(s2) == np.array(s)).all() and (np.array(it2) == np.array(it)).all(), kw
+    assert n <= may, (kw, tunables, "re-runs", n, "exceed what the lane and mid kernels may hand back", may)
+    b.free()
+    eng.close()
 
 
 def test_mid_kernel_serves_single_calls(oracle):
