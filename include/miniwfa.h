@@ -165,6 +165,65 @@ int32_t mwf_gpu_batch_cigar(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t i, uint32_
 /* Optional: bring every CIGAR of the batch to the host in one copy; mwf_gpu_batch_cigar then serves from that copy. */
 int mwf_gpu_batch_fetch_cigars(mwf_gpu_t *g, mwf_gpu_batch_t *b);
 
+/* ---- After the align: summaries, CIGAR checks and coordinate maps without leaving the device (kernels: csrc/mwf_cigar_ops.hip) ---- */
+
+/* What a CIGAR says about its pair, and whether it is an alignment of THESE sequences: the counters a caller derives identity and
+ * gap statistics from, plus the self-check the reference's CLI runs on every record (mwf_assert_cigar) extended to the bases. */
+typedef struct {            /* 48 bytes, twelve int32 */
+	int32_t score;          /* what mwf_cigar2score gives for the words under the options used */
+	int32_t t_len, q_len;   /* bases of target / query the words consume */
+	int32_t n_eq, n_x;      /* bases under '=' / 'X' */
+	int32_t n_ins, n_del;   /* bases under 'I' (query only) / 'D' (target only) */
+	int32_t n_ins_runs, n_del_runs; /* words with op I / D (each pays one gap open in `score`) */
+	int32_t n_words;        /* words summarised */
+	int32_t first_bad;      /* -1: the words are a valid alignment of THESE sequences; else see below */
+	int32_t flags;          /* bit 0: the pair has a CIGAR (otherwise every other field is 0 and first_bad is -1); other bits 0 */
+} mwf_aln_summary_t;
+/* first_bad: walk the words in order with running start positions (ti, qj), kept in 64 bits; every word with a known op (1 I, 2 D,
+ * 7 =, 8 X) advances them by its full length, whatever else is wrong with it.  Word w is bad if (a) its op is none of those four
+ * (such a word consumes nothing and counts nowhere), or (b) it runs past the end of a sequence (ti+len > tl for D, = and X; qj+len > ql
+ * for I, = and X), or (c) it is = or X and some base of its in-range part contradicts the op (t[ti+k] != q[qj+k] under =, equal under X,
+ * for k < min(len, tl-ti, ql-qj)).  first_bad is the smallest bad w; without one it is n_words if (ti, qj) != (tl, ql), else -1.
+ * score and the counters accumulate in 64 bits from the full word lengths and are truncated on store. */
+
+/* The host twin: the summary of one CIGAR against one pair of sequences.  Needs no device.  Never reads outside ts[0,tl) / qs[0,ql),
+ * whatever the words say.  flags is always 1 here (n_cigar == 0 is an empty CIGAR: first_bad 0 unless both sequences are empty). */
+void mwf_cigar_summary(const mwf_opt_t *opt, int32_t n_cigar, const uint32_t *cigar, int32_t tl, const char *ts, int32_t ql, const char *qs,
+                       mwf_aln_summary_t *out);
+
+/* Zero-copy access to the CIGARs of the batch's last CIGAR-mode align: finalises the batch as mwf_gpu_batch_results() does, then hands out
+ * device pointers: pair i's words are pool[word_off[i] .. word_off[i] + n_words[i]).  The pool is unordered and has holes: only word_off
+ * and n_words address it; *pool_words is how many words from `pool` on are in use (holes included).  Valid until the next align or free
+ * of the batch.  Any output pointer may be NULL.  Fails (negative; mwf_gpu_last_error) if the last align was score-only. */
+int mwf_gpu_batch_dev_cigars(mwf_gpu_t *g, mwf_gpu_batch_t *b, const uint32_t **pool, const int64_t **word_off, const int32_t **n_words, int64_t *pool_words);
+
+/* Enqueue the summary kernel on the engine's stream: one mwf_aln_summary_t per pair into a library-owned device array; returns without
+ * waiting for the kernel.  opt == NULL: the options of the last align (only x, o1, e1, o2, e2 are used).
+ * d_words, d_word_off, d_n_words all NULL: the batch's own CIGARs — the call finalises the batch first (and waits for that), a pair has a
+ * CIGAR when its status is 0 (a stopped pair's record has flags == 0), and the call fails if the last align was score-only.
+ * Otherwise all three are caller-owned device arrays: foreign CIGARs for the batch's sequences (stitched chain-mode CIGARs, another
+ * aligner's), pair i's words at d_words[d_word_off[i] .. + d_n_words[i]); they are trusted only to lie inside the caller's allocation —
+ * malformed words yield a record (first_bad), never a read outside a pair's sequences.  A pair with d_n_words[i] <= 0 has no CIGAR.
+ * Work the caller enqueued on other streams (the tensors' producer) must be complete. */
+int mwf_gpu_batch_summarize(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const uint32_t *d_words, const int64_t *d_word_off, const int32_t *d_n_words);
+/* Device pointer to the n records of the last summarize; NULL before the first one and after a newer align made them stale. */
+const mwf_aln_summary_t *mwf_gpu_batch_dev_summary(const mwf_gpu_batch_t *b);
+/* Wait and copy the n records to host_out. */
+int mwf_gpu_batch_summary(mwf_gpu_t *g, mwf_gpu_batch_t *b, mwf_aln_summary_t *host_out);
+
+/* Coordinate maps of the batch's own CIGARs (finalises; fails after a score-only align).  which 0: query -> target, 1: target -> query.
+ * A map is a dense int32 array in pair order: pair i occupies [off[i], off[i] + ql[i]) (which 0) or [off[i], off[i] + tl[i]) (which 1),
+ * off = exclusive prefix sum of those lengths.  A base under = or X holds the index of its partner; a query base under I holds
+ * -1 - t_next, t_next in 0 .. tl being the next target base to be consumed (a target base under D: -1 - q_next); every position of a pair
+ * without a CIGAR (stopped, s == -1) holds INT32_MIN.  Writes are clipped to the pair's range.  _map enqueues the kernel and returns. */
+int mwf_gpu_batch_map(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which);
+/* Device pointer to that map; NULL before the first mwf_gpu_batch_map(.., which) and after a newer align. */
+const int32_t *mwf_gpu_batch_dev_map(const mwf_gpu_batch_t *b, int32_t which);
+/* Wait and copy the map to host_out (sum of the lengths int32) and, unless NULL, its n + 1 offsets to host_off. */
+int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int32_t *host_out, int64_t *host_off);
+/* The summary array and the maps are allocated on first use through the engine's accounting (mwf_gpu_stats_t dev_bytes / dev_bytes_peak
+ * include them while the batch lives) and freed with the batch; a caller that never asks pays nothing. */
+
 /* Timing and counters of the most recent mwf_gpu_batch_align on this engine. */
 typedef struct {
 	double  kernel_ms;     /* HIP-event time around the alignment kernels on the engine's stream */

@@ -43,6 +43,25 @@ class GpuStats(C.Structure):
                 ("dev_bytes", C.c_int64), ("dev_bytes_peak", C.c_int64), ("packed", C.c_int32), ("lowmem_two_pass", C.c_int32)]
 
 
+class AlnSummary(C.Structure):
+    """mwf_aln_summary_t (include/miniwfa.h), 48 bytes: what a CIGAR says about its pair and whether it aligns THESE sequences."""
+    _fields_ = [("score", C.c_int32), ("t_len", C.c_int32), ("q_len", C.c_int32), ("n_eq", C.c_int32), ("n_x", C.c_int32),
+                ("n_ins", C.c_int32), ("n_del", C.c_int32), ("n_ins_runs", C.c_int32), ("n_del_runs", C.c_int32),
+                ("n_words", C.c_int32), ("first_bad", C.c_int32), ("flags", C.c_int32)]
+
+
+# the same record as a numpy structured dtype: Batch.summary() returns an array of it
+SUMMARY_DTYPE = np.dtype([(name, "<i4") for name, _ in AlnSummary._fields_])
+
+
+class DevArray:
+    """A device buffer owned by the library (or anyone) as a __cuda_array_interface__ object: torch.as_tensor(DevArray(ptr, n, "<i4"),
+    device=...) is a zero-copy tensor over it.  typestr as in numpy ("<i4", "<i8", "<u4", "|u1"); the buffer must outlive the tensor."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2}
+
+
 class KmStat(C.Structure):
     _fields_ = [("capacity", C.c_size_t), ("available", C.c_size_t), ("n_blocks", C.c_size_t),
                 ("n_cores", C.c_size_t), ("largest", C.c_size_t)]
@@ -55,6 +74,8 @@ ABI_SYMBOLS = (
     "mwf_gpu_batch_upload", "mwf_gpu_batch_wrap", "mwf_gpu_batch_free", "mwf_gpu_batch_align", "mwf_gpu_batch_results",
     "mwf_gpu_batch_dev_scores", "mwf_gpu_batch_dev_iters", "mwf_gpu_batch_cigar", "mwf_gpu_get_stats", "mwf_gpu_set",
     "mwf_gpu_debug_band",
+    "mwf_cigar_summary", "mwf_gpu_batch_dev_cigars", "mwf_gpu_batch_summarize", "mwf_gpu_batch_dev_summary", "mwf_gpu_batch_summary",
+    "mwf_gpu_batch_map", "mwf_gpu_batch_dev_map", "mwf_gpu_batch_map_fetch",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -134,6 +155,22 @@ def lib() -> C.CDLL:
     L.mwf_gpu_test_pair_sketch.restype = C.c_int
     L.mwf_gpu_debug_band.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), C.c_int32, C.c_void_p, C.c_int32]
     L.mwf_gpu_debug_band.restype = C.c_int32
+    L.mwf_cigar_summary.argtypes = [P(MwfOpt), C.c_int32, C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, P(AlnSummary)]
+    L.mwf_cigar_summary.restype = None
+    L.mwf_gpu_batch_dev_cigars.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_int64)]
+    L.mwf_gpu_batch_dev_cigars.restype = C.c_int
+    L.mwf_gpu_batch_summarize.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_summarize.restype = C.c_int
+    L.mwf_gpu_batch_dev_summary.argtypes = [C.c_void_p]
+    L.mwf_gpu_batch_dev_summary.restype = C.c_void_p
+    L.mwf_gpu_batch_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_summary.restype = C.c_int
+    L.mwf_gpu_batch_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.mwf_gpu_batch_map.restype = C.c_int
+    L.mwf_gpu_batch_dev_map.argtypes = [C.c_void_p, C.c_int32]
+    L.mwf_gpu_batch_dev_map.restype = C.c_void_p
+    L.mwf_gpu_batch_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_map_fetch.restype = C.c_int
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
                             ("krealloc", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t]), ("krelocate", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t]),
                             ("kfree", None, [C.c_void_p, C.c_void_p]), ("km_init", C.c_void_p, []), ("km_init2", C.c_void_p, [C.c_void_p, C.c_size_t]),
@@ -281,6 +318,14 @@ def cigar2score(opt: MwfOpt, cigar: Sequence[int]):
     return s, tl.value, ql.value
 
 
+def cigar_summary(t: bytes, q: bytes, opt: MwfOpt, cigar: Sequence[int]) -> np.void:
+    """mwf_cigar_summary, the host twin of Batch.summary(): one SUMMARY_DTYPE record for `cigar` (words len<<4|op) against (t, q).  Needs no device."""
+    words = np.ascontiguousarray(np.asarray(cigar, dtype=np.uint32))
+    out = AlnSummary()
+    lib().mwf_cigar_summary(C.byref(opt), len(words), words.ctypes.data if len(words) else None, len(t), t, len(q), q, C.byref(out))
+    return np.frombuffer(bytes(out), dtype=SUMMARY_DTYPE)[0]
+
+
 class Engine:
     """mwf_gpu_t: one device, one stream, one workspace pool."""
 
@@ -404,6 +449,58 @@ class Batch:
         rc = lib().mwf_gpu_batch_fetch_cigars(self.eng.h, self.h)
         if rc != 0:
             raise RuntimeError(f"CIGAR download failed ({rc}): " + self.eng.error())
+
+    def dev_cigars(self):
+        """(pool_ptr, off_ptr, n_words_ptr, pool_words): the device arrays of the last CIGAR-mode align, zero-copy (mwf_gpu_batch_dev_cigars).
+        Pair i's words are pool[off[i] : off[i] + n_words[i]] (uint32 / int64 / int32); valid until the next align or free of the batch."""
+        pool, off, nw, used = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        rc = lib().mwf_gpu_batch_dev_cigars(self.eng.h, self.h, C.byref(pool), C.byref(off), C.byref(nw), C.byref(used))
+        if rc != 0:
+            raise RuntimeError(f"dev_cigars failed ({rc}): " + self.eng.error())
+        return pool.value or 0, off.value or 0, nw.value or 0, used.value
+
+    def summarize(self, opt: MwfOpt | None = None, cigars=None):
+        """Enqueue the summary kernel (mwf_gpu_batch_summarize) and return; dev_summary_ptr() then points at the n records.  cigars: None for
+        the batch's own CIGARs, or (words_ptr, off_ptr, n_words_ptr) device arrays of foreign ones (uint32 / int64 / int32)."""
+        w, o, c = cigars if cigars is not None else (None, None, None)
+        rc = lib().mwf_gpu_batch_summarize(self.eng.h, self.h, C.byref(opt) if opt is not None else None, w, o, c)
+        if rc != 0:
+            raise RuntimeError(f"summarize failed ({rc}): " + self.eng.error())
+
+    def summary(self, opt: MwfOpt | None = None, cigars=None) -> np.ndarray:
+        """summarize() + wait + copy: a structured array (SUMMARY_DTYPE) of n records."""
+        self.summarize(opt, cigars)
+        out = np.zeros(self.n, dtype=SUMMARY_DTYPE)
+        rc = lib().mwf_gpu_batch_summary(self.eng.h, self.h, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"summary download failed ({rc}): " + self.eng.error())
+        return out
+
+    def dev_summary_ptr(self) -> int | None:
+        """Device pointer to the records of the last summarize(); None before the first one and after a newer align."""
+        return lib().mwf_gpu_batch_dev_summary(self.h)
+
+    def map(self, which: int):
+        """Enqueue the coordinate-map kernel (mwf_gpu_batch_map; which 0: query -> target, 1: target -> query) and return."""
+        rc = lib().mwf_gpu_batch_map(self.eng.h, self.h, which)
+        if rc != 0:
+            raise RuntimeError(f"map failed ({rc}): " + self.eng.error())
+
+    def coord_map(self, which: int):
+        """map() + wait + copy -> (values[int32], offsets[int64, n + 1]): pair i's slice is values[offsets[i]:offsets[i + 1]] (include/miniwfa.h)."""
+        self.map(which)
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        rc = lib().mwf_gpu_batch_map_fetch(self.eng.h, self.h, which, None, off.ctypes.data)
+        vals = np.zeros(int(off[-1]), dtype=np.int32)
+        if rc == 0 and len(vals):
+            rc = lib().mwf_gpu_batch_map_fetch(self.eng.h, self.h, which, vals.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError(f"map download failed ({rc}): " + self.eng.error())
+        return vals, off
+
+    def dev_map_ptr(self, which: int) -> int | None:
+        """Device pointer to the map of the last map(which); None before the first one and after a newer align."""
+        return lib().mwf_gpu_batch_dev_map(self.h, which)
 
     def work_sketch(self) -> np.ndarray:
         """hits[i]: 8-mers of pair i's query that occur in its target — the per-pair work estimate the band classes are dealt by (test hook)."""

@@ -43,4 +43,44 @@ void mwf_assert_cigar(const mwf_opt_t *opt, int32_t n_cigar, const uint32_t *cig
 	if (s > s0) fprintf(stderr, "[mwf_assert_cigar] s0=%d, s=%d\n", s0, s);
 }
 
+// Host twin of the device summary (mwf_cigar_ops.hip): counters and score as mwf_cigar2score counts them (ops 1, 2, 7, 8 only), and
+// first_bad by the rule in include/miniwfa.h.  Positions run in 64 bits; a base is only ever read at an index below its sequence's length.
+void mwf_cigar_summary(const mwf_opt_t *opt, int32_t n_cigar, const uint32_t *cigar, int32_t tl, const char *ts, int32_t ql, const char *qs,
+                       mwf_aln_summary_t *out)
+{
+	int64_t ti = 0, qj = 0; // (below 2^59 for any int32 count of 28-bit lengths)
+	uint64_t score = 0; // (wraps, never overflows: only its low 32 bits are stored)
+	int64_t n_eq = 0, n_x = 0, n_ins = 0, n_del = 0, ins_runs = 0, del_runs = 0;
+	int32_t first_bad = -1;
+	if (n_cigar < 0) n_cigar = 0;
+	for (int32_t w = 0; w < n_cigar; ++w) {
+		const int32_t op = (int32_t)(cigar[w] & 0xf);
+		const int64_t len = (int64_t)(cigar[w] >> 4);
+		bool bad = false;
+		if (op == 1 || op == 2) {
+			const int64_t p1 = opt->o1 + len * opt->e1, p2 = opt->o2 + len * opt->e2;
+			score += (uint64_t)(p1 < p2 ? p1 : p2);
+			if (op == 1) bad = qj + len > ql, n_ins += len, ++ins_runs, qj += len;
+			else bad = ti + len > tl, n_del += len, ++del_runs, ti += len;
+		} else if (op == 7 || op == 8) {
+			bad = ti + len > tl || qj + len > ql;
+			if (!bad && first_bad < 0) { // (the bases decide nothing once an earlier word is bad)
+				const int64_t room_t = ti < tl ? tl - ti : 0, room_q = qj < ql ? ql - qj : 0;
+				const int64_t m = len < room_t ? (len < room_q ? len : room_q) : (room_t < room_q ? room_t : room_q);
+				for (int64_t k = 0; k < m && !bad; ++k) bad = (ts[ti + k] == qs[qj + k]) != (op == 7);
+			}
+			if (op == 8) score += (uint64_t)(len * opt->x), n_x += len;
+			else n_eq += len;
+			ti += len, qj += len;
+		} else bad = true;
+		if (bad && first_bad < 0) first_bad = w;
+	}
+	if (first_bad < 0 && (ti != tl || qj != ql)) first_bad = n_cigar;
+	auto low32 = [](int64_t v) { return (int32_t)(uint32_t)(uint64_t)v; };
+	out->score = (int32_t)(uint32_t)score, out->t_len = low32(ti), out->q_len = low32(qj);
+	out->n_eq = low32(n_eq), out->n_x = low32(n_x), out->n_ins = low32(n_ins), out->n_del = low32(n_del);
+	out->n_ins_runs = low32(ins_runs), out->n_del_runs = low32(del_runs);
+	out->n_words = n_cigar, out->first_bad = first_bad, out->flags = 1;
+}
+
 } // extern "C"

@@ -182,6 +182,7 @@ void mwf_gpu_batch_free(mwf_gpu_batch_t *b)
 	if (g->res_pin_owner == b) g->res_pin_owner = nullptr;
 	give_block(g, g->spare_block, b->block);
 	give_block(g, g->spare_cig, b->cig);
+	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1]}) release(g, *d); // (hipFree waits for a kernel still writing them)
 	delete b;
 }
 
@@ -224,6 +225,123 @@ int mwf_gpu_batch_fetch_cigars(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 	if (!g || !b) return -1;
 	(void)hipSetDevice(g->device);
 	return fetch_cigars(g, b);
+}
+
+/* ------------------------------------------------------------------ summaries, CIGAR checks, coordinate maps (mwf_cigar_ops.hip) */
+
+// the batch's own CIGARs are there: finalised, and the last align produced them
+static int own_cigars(mwf_gpu_t *g, mwf_gpu_batch_t *b, const char *who)
+{
+	if (int rc = finalize(g, b)) return rc;
+	if (!(b->opt.flag & MWF_F_CIGAR)) { g->err = std::string(who) + ": the batch's last align was score-only (no CIGARs to work on; align with MWF_F_CIGAR)"; return -2; }
+	return 0;
+}
+
+static int ops_block(mwf_gpu_batch_t *b)
+{
+	if (b->ops_max_len < 0) {
+		b->ops_max_len = 0;
+		for (int32_t i = 0; i < b->n; ++i) b->ops_max_len = std::max<int64_t>(b->ops_max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+	}
+	return cigar_ops_block(b->ops_max_len);
+}
+
+static CigarOpsArgs ops_args(const mwf_gpu_batch_t *b)
+{
+	CigarOpsArgs a{};
+	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql, a.n_pairs = b->n;
+	a.words = b->d_cig_pool, a.word_off = b->d_cigoff, a.n_words = b->d_ncig, a.status = b->d_status;
+	return a;
+}
+
+int mwf_gpu_batch_dev_cigars(mwf_gpu_t *g, mwf_gpu_batch_t *b, const uint32_t **pool, const int64_t **word_off, const int32_t **n_words, int64_t *pool_words)
+{
+	if (!g || !b) return -1;
+	(void)hipSetDevice(g->device);
+	if (int rc = own_cigars(g, b, "mwf_gpu_batch_dev_cigars")) return rc;
+	if (pool) *pool = b->d_cig_pool;
+	if (word_off) *word_off = b->d_cigoff;
+	if (n_words) *n_words = b->d_ncig;
+	if (pool_words) *pool_words = b->n > 0 ? b->cig_used : 0;
+	return 0;
+}
+
+int mwf_gpu_batch_summarize(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const uint32_t *d_words, const int64_t *d_word_off, const int32_t *d_n_words)
+{
+	if (!g || !b) return -1;
+	(void)hipSetDevice(g->device);
+	const bool own = !d_words && !d_word_off && !d_n_words;
+	if (!own && (!d_words || !d_word_off || !d_n_words)) { g->err = "mwf_gpu_batch_summarize: foreign CIGARs need all three device arrays (words, offsets, counts)"; return -2; }
+	if (own) { if (int rc = own_cigars(g, b, "mwf_gpu_batch_summarize")) return rc; }
+	else if (b->busy) HIP_TRY(g, hipStreamSynchronize(g->stream)); // (an align nobody waited for: its follow-up work is the host's, in finalize — keep the order simple)
+	if (!opt && !b->aligned) { g->err = "mwf_gpu_batch_summarize: opt == NULL needs an earlier align of the batch"; return -2; }
+	const mwf_opt_t &o = opt ? *opt : b->opt;
+	b->summary_valid = false;
+	if (b->n == 0) { b->summary_valid = true; return 0; }
+	if (ensure(g, b->ops_summary, (size_t)b->n * sizeof(mwf_aln_summary_t))) return -1;
+	CigarOpsArgs a = ops_args(b);
+	if (!own) a.words = d_words, a.word_off = d_word_off, a.n_words = d_n_words, a.status = nullptr;
+	a.x = o.x, a.o1 = o.o1, a.e1 = o.e1, a.o2 = o.o2, a.e2 = o.e2;
+	a.mode = 0, a.summary = (int32_t*)b->ops_summary.p;
+	if (launch_cigar_ops(a, ops_block(b), g->stream)) { g->err = "kernel launch failed (CIGAR summary)"; return -1; }
+	b->summary_valid = true;
+	return 0;
+}
+
+const mwf_aln_summary_t *mwf_gpu_batch_dev_summary(const mwf_gpu_batch_t *b)
+{
+	return b && b->summary_valid ? (const mwf_aln_summary_t*)b->ops_summary.p : nullptr;
+}
+
+int mwf_gpu_batch_summary(mwf_gpu_t *g, mwf_gpu_batch_t *b, mwf_aln_summary_t *host_out)
+{
+	if (!g || !b || !host_out) return -1;
+	(void)hipSetDevice(g->device);
+	if (!b->summary_valid) { g->err = "mwf_gpu_batch_summary: no summary (call mwf_gpu_batch_summarize after the align)"; return -2; }
+	return download(g, host_out, b->ops_summary.p, (size_t)b->n * sizeof(mwf_aln_summary_t));
+}
+
+int mwf_gpu_batch_map(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which)
+{
+	if (!g || !b || which < 0 || which > 1) return -1;
+	(void)hipSetDevice(g->device);
+	if (int rc = own_cigars(g, b, "mwf_gpu_batch_map")) return rc;
+	b->map_valid[which] = false;
+	std::vector<int64_t> &off = b->h_map_off[which];
+	if (off.empty()) {
+		off.assign((size_t)b->n + 1, 0);
+		for (int32_t i = 0; i < b->n; ++i) off[i + 1] = off[i] + (which == 0 ? b->h_ql[i] : b->h_tl[i]);
+	}
+	if (b->n == 0) { b->map_valid[which] = true; return 0; }
+	if (ensure(g, b->ops_map[which], std::max<size_t>((size_t)off[b->n] * 4, 256))) return -1;
+	// the device copy of the offsets is tracked on its own: a call that failed after the host vector was filled (the map is the largest
+	// buffer here) must not make the next one launch on offsets that were never uploaded
+	if (!b->map_off_uploaded[which]) {
+		if (ensure(g, b->ops_map_off[which], ((size_t)b->n + 1) * 8)) return -1;
+		if (upload_segments(g, (char*)b->ops_map_off[which].p, std::vector<Seg>{Seg{off.data(), ((size_t)b->n + 1) * 8}})) return -1;
+		b->map_off_uploaded[which] = true;
+	}
+	CigarOpsArgs a = ops_args(b);
+	a.mode = 1 + which, a.map = (int32_t*)b->ops_map[which].p, a.map_off = (const int64_t*)b->ops_map_off[which].p;
+	if (launch_cigar_ops(a, ops_block(b), g->stream)) { g->err = "kernel launch failed (coordinate map)"; return -1; }
+	b->map_valid[which] = true;
+	return 0;
+}
+
+const int32_t *mwf_gpu_batch_dev_map(const mwf_gpu_batch_t *b, int32_t which)
+{
+	return b && which >= 0 && which <= 1 && b->map_valid[which] ? (const int32_t*)b->ops_map[which].p : nullptr;
+}
+
+int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int32_t *host_out, int64_t *host_off)
+{
+	if (!g || !b || which < 0 || which > 1) return -1;
+	(void)hipSetDevice(g->device);
+	if (!b->map_valid[which]) { g->err = "mwf_gpu_batch_map_fetch: no map (call mwf_gpu_batch_map after the align)"; return -2; }
+	const std::vector<int64_t> &off = b->h_map_off[which];
+	if (host_off) memcpy(host_off, off.data(), off.size() * 8);
+	if (!host_out || b->n == 0) { HIP_TRY(g, hipStreamSynchronize(g->stream)); return 0; }
+	return download(g, host_out, b->ops_map[which].p, (size_t)off[b->n] * 4);
 }
 
 /* test hook: trace the band of one pair (columns lo,hi per penalty); returns penalties traced */

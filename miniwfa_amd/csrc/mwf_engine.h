@@ -190,6 +190,12 @@ struct mwf_gpu_batch_s {
 	bool dev_retry_used = false;     // this align made such a follow-up launch: the count is added to n_retries
 	// debug band trace (tests)
 	int32_t debug_pair = -1;
+	// products of mwf_cigar_ops.hip (summary, coordinate maps): allocated on first use, stale after the next align, freed with the batch
+	DevBuf ops_summary, ops_map[2], ops_map_off[2];
+	bool summary_valid = false, map_valid[2] = {false, false};
+	std::vector<int64_t> h_map_off[2]; // n + 1 offsets into the map (which 0: prefix sums of ql, 1: of tl); empty until first asked for
+	bool map_off_uploaded[2] = {false, false}; // ops_map_off[which] holds h_map_off[which] (set only after the upload succeeded)
+	int64_t ops_max_len = -1;          // longest pair (tl + ql): what the workgroup size of those kernels is chosen by (-1: not computed yet)
 };
 
 

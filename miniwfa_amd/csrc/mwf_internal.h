@@ -145,7 +145,25 @@ int launch_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, 
 // the same statistic over the WHOLE sequences of every pair order[0 .. n) (order null: pairs 0 .. n; one workgroup each): out[k] = 8-mers of that pair's query that occur
 // in its target (the work estimate the band classes are dealt by, mwf_plan.cpp)
 int launch_pair_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, const int32_t *order, int32_t n, int32_t *out, void *stream);
-int  bigring_kernel_occupancy();                      // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
+// mwf_cigar_ops.hip: summary / self-check and coordinate maps of a batch's CIGARs (one workgroup per pair; off the align path)
+struct CigarOpsArgs {
+	const uint8_t *seqs;
+	const int64_t *t_off, *q_off;
+	const int32_t *tl, *ql;
+	int32_t n_pairs;
+	const uint32_t *words;     // pair i's words: words[word_off[i] .. word_off[i] + n_words[i])
+	const int64_t *word_off;
+	const int32_t *n_words;
+	const int32_t *status;     // the batch's own CIGARs: a pair has one when status[i] == ST_OK; null (foreign CIGARs): when n_words[i] > 0
+	int32_t x, o1, e1, o2, e2; // summary: the penalties `score` is counted under
+	int32_t mode;              // 0: summary; 1: map query -> target; 2: map target -> query
+	int32_t *summary;          // mode 0: [pair][12], the fields of mwf_aln_summary_t in order
+	int32_t *map;              // modes 1, 2: pair i's slice starts at map[map_off[i]]
+	const int64_t *map_off;
+};
+int cigar_ops_block(int64_t max_len);                 // threads per pair for a batch whose longest pair has max_len bases of target + query
+int launch_cigar_ops(const CigarOpsArgs &a, int block, void *stream);
+int  bigring_kernel_occupancy();                     // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
 int  batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ring16);   // resident workgroups per CU for that block size
 
 // geometry of a launch of the band family (mwf_band2.hip packed band kernel, mwf_lane.hip, mwf_mid.hip)
