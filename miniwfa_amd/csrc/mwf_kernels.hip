@@ -1297,34 +1297,42 @@ static int launch_batch_as(const BatchArgs &a, int grid, int block, hipStream_t 
 // E2/F2 in LDS: one 512-thread workgroup per CU with 2 x lds_e2_cols ints of dynamic LDS
 static bool wants_lds2(const BatchArgs &a, int block) { return wants_stream(a) && a.lds_e2_cols > 0 && (block == 512 || block == 768) && a.pen.e2 == 1; }
 
+// MWF_DEBUG: the template arguments of the generic kernel a launch takes (tests/generic_matrix.py reads this line)
+static void record_launch(const BatchArgs &a, int grid, int T, bool stream_form, bool lds2, bool h16, int mode, bool big)
+{
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] generic launch: T %d STREAM %d LDS2 %d H16 %d MODE %d BIG %d, lds_cols %d, %d pairs, grid %d\n", T, (int)stream_form, (int)lds2, (int)h16, mode, (int)big,
+		        lds2 ? (int)a.lds_e2_cols : 0, (int)a.n_pairs, grid);
+}
+
 int launch_batch(const BatchArgs &a, int grid, int block, void *stream)
 {
 	if (a.pen.nH > kMaxRing) { // a ring deeper than the LDS window tables of every other kernel
 		if (a.pen.nH > kBigRing) return -1;
+		record_launch(a, grid, 256, false, false, false, -1, true);
 		hipLaunchKernelGGL(wfa_bigring_kernel<256>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
 		return hipGetLastError() == hipSuccess ? 0 : -2;
 	}
 	if (wants_lds2(a, block)) {
+		// the plan (run_batch_kernel) takes 768 threads with 32-bit rows and for traceback on 16-bit rows, 512 threads score-only on 16-bit rows: the
+		// four forms below are the ones it can ask for
 		const int lds = a.lds_e2_cols * 2 * (a.ring16 ? 2 : 4); // E2 and F2, as 16-bit codes with the 16-bit ring rows
 		const int lds_max = a.lds_e2_cols * 2 * 4;
 		auto go = [&](auto kernel, int threads) {
+			record_launch(a, grid, threads, true, true, a.ring16 != 0, a.want_cigar ? 1 : 0, false);
 			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
 			(void)hipGetLastError();
 			hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, (hipStream_t)stream, a);
 		};
-		if (a.want_cigar) {
-			if (a.ring16 && block == 768) go(&wfa_batch_kernel<768, true, true, true, 1>, 768);
-			else if (a.ring16) go(&wfa_batch_kernel<512, true, true, true, 1>, 512);
-			else if (block == 768) go(&wfa_batch_kernel<768, true, true, false, 1>, 768);
-			else go(&wfa_batch_kernel<512, true, true, false, 1>, 512);
-		} else {
-			if (a.ring16 && block == 768) go(&wfa_batch_kernel<768, true, true, true, 0>, 768);
-			else if (a.ring16) go(&wfa_batch_kernel<512, true, true, true, 0>, 512);
-			else if (block == 768) go(&wfa_batch_kernel<768, true, true, false, 0>, 768);
-			else go(&wfa_batch_kernel<512, true, true, false, 0>, 512);
-		}
+		if (a.ring16 && a.want_cigar && block == 768) go(&wfa_batch_kernel<768, true, true, true, 1>, 768);
+		else if (a.ring16 && !a.want_cigar && block == 512) go(&wfa_batch_kernel<512, true, true, true, 0>, 512);
+		else if (!a.ring16 && a.want_cigar && block == 768) go(&wfa_batch_kernel<768, true, true, false, 1>, 768);
+		else if (!a.ring16 && block == 768) go(&wfa_batch_kernel<768, true, true, false, 0>, 768);
+		else return -1; // (no such form is built)
 		return hipGetLastError() == hipSuccess ? 0 : -2;
 	}
+	if (block != 64 && block != 128 && block != 256 && block != 512 && block != 1024) return -1;
+	record_launch(a, grid, block, wants_stream(a), false, false, -1, false);
 	return wants_stream(a) ? launch_batch_as<true>(a, grid, block, (hipStream_t)stream) : launch_batch_as<false>(a, grid, block, (hipStream_t)stream);
 }
 
@@ -1356,11 +1364,12 @@ int batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ri
 		int n = 0;
 		const size_t lds = (size_t)lds_e2_cols * (ring16 ? 4 : 8);
 		hipError_t e;
-		// (the traceback kernels: the score-only ones never hold fewer workgroups)
+		// (the forms the plan launches: with 32-bit rows the traceback kernel on 768 threads — its score-only twin never holds fewer workgroups —, with 16-bit
+		// rows the traceback kernel on 768 and the score-only one on 512)
 		if (ring16) e = block == 768 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<768, true, true, true, 1>, 768, lds)
-		                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<512, true, true, true, 1>, 512, lds);
-		else e = block == 768 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<768, true, true, false, 1>, 768, lds)
-		                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<512, true, true, false, 1>, 512, lds);
+		                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<512, true, true, true, 0>, 512, lds);
+		else if (block == 768) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<768, true, true, false, 1>, 768, lds);
+		else return 0;
 		return e == hipSuccess ? n : 0;
 	}
 	return stream_pass ? occupancy_as<true>(block) : occupancy_as<false>(block);
