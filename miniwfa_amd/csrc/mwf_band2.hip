@@ -423,6 +423,22 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 #pragma unroll
 	for (int k = 0; k < K; ++k) idle[k] = kAgeOut;
 	int32_t up_wait = 0, up_min = 0; // penalties for which the window has started above chunk gl, the lowest start among them
+	// Window epoch.  What a penalty's header derives about this wave's slots depends only on the chunks the window meets, ga = lo >> 8 and
+	// gb = hi >> 8, on the mapping start gl and on the slots' ages — and an edge moves one column per penalty, so the same answers hold for
+	// about a hundred penalties on end.  The header therefore keeps them in one scalar, `est`, together with the key they were derived for
+	// (`ekey`: gl_next, gb and ga - gl_next packed, or 0), and a penalty whose key is the same reuses them (the fast header): no activity
+	// compares, no priority ladder (the priority persists by itself), no overflow tests, no remap comparison behind the barrier.  The key
+	// is only kept when nothing else is in motion: no slot ageing, no remap pending (gl_next == gl, up_wait == 0), the coarse overflow and
+	// three-slot tests false, i.e. false for every window with these chunks.  Every other penalty runs the full header.
+	// est: per slot k bits 4k..4k+3 = runs | holds the lo edge (g == ga) | holds the hi edge (g == gb) | ageing (outside the window);
+	// bit 24 / 25: this wave stores the dead chunk below / above the window.
+	int32_t ekey = 0;
+	// Gated off, i.e. the full header every penalty: the span geometry (the cached word costs its folded score-only form its last free register — scratch where it had
+	// none) and the 64-thread geometry (one wave per pair: nothing is repeated eight times, and 2048 x 400 bp measured 0.366 -> 0.404 ms with the fast header).
+	constexpr bool kEpoch = !is_span(T, K) && T != 64;
+	uint32_t est = 0;
+	static_assert(kEpoch || ((NW & (NW - 1)) == 0 && !(T == 512 && K == 4)), "the full header of the gated geometries is written for a power-of-two wave count and no three-slot note");
+	static_assert(K <= 6, "slot classes of the window epoch: four bits per slot below bit 24");
 
 	// One penalty; returns true when the pass ends.  A depth-2 history is two registers, [0] the newer: the penalty reads [1] for the last
 	// time, overwrites it, and the two trade places (v_swap_b32) — no copies, and a slot that is skipped leaves its registers alone.
@@ -447,14 +463,74 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		}
 		// the window of penalty s_new+1 lies inside [lo-1, hi+1] whatever the flags say; it must fit the register span
 		const int32_t gl_next = (lo > 1 ? lo - 1 : 1) >> 8;
-		// (the mapping follows a window that moves UP kAgeOut penalties late — the chunks it leaves behind still run, see below)
-		if ((hi >> 8) - min(lo >> 8, gl + 1) + 3 > NWK - 1) // (only then can the exact test fail)
-			if (((hi < cmax ? hi + 1 : cmax) >> 8) - min(gl_next, gl) + 1 > NWK - 1) { R.status = ST_BAND_OVERFLOW; return true; }
-		// (the four-slot form of the 512-thread geometry notes whether the three-slot form would have held the pair: the host's choice for the next align)
-		if (T == 512 && K == 4 && (hi >> 8) - (lo >> 8) + 3 > 23)
-			if (((hi < cmax ? hi + 1 : cmax) >> 8) - gl_next + 1 > 23) R.n_snap = 1;
-		// (biased offsets, sequences beyond 32 kb: the room arithmetic holds ql - d in 16 unsigned bits)
-		if (BI && cmax - lo > 65535) { R.status = ST_BAND_OVERFLOW; return true; }
+		const int32_t ga = lo >> 8, gb = hi >> 8; // chunks [ga, gb] meet the window
+		const int32_t key = gl_next | gb << 15 | 1 << 29 | (ga - gl_next) << 30; // (never 0, never negative)
+		const bool fast = kEpoch && key == ekey; // uniform: the slot state of the last full header holds
+		uint32_t st = est;
+		bool act[K]; // (only where the epoch is gated off)
+		if (!kEpoch) {
+			if (gb - min(ga, gl + 1) + 3 > NWK - 1) // (only then can the exact test fail)
+				if (((hi < cmax ? hi + 1 : cmax) >> 8) - min(gl_next, gl) + 1 > NWK - 1) { R.status = ST_BAND_OVERFLOW; return true; }
+			if (BI && cmax - lo > 65535) { R.status = ST_BAND_OVERFLOW; return true; }
+		} else if (!fast) {
+			bool hold = true; // may the coming penalties reuse what this header derives?
+			// (the mapping follows a window that moves UP kAgeOut penalties late — the chunks it leaves behind still run, see below)
+			if (gb - min(ga, gl + 1) + 3 > NWK - 1) { // (only then can the exact test fail)
+				if (((hi < cmax ? hi + 1 : cmax) >> 8) - min(gl_next, gl) + 1 > NWK - 1) { R.status = ST_BAND_OVERFLOW; return true; }
+				hold = false;
+			}
+			// (the four-slot form of the 512-thread geometry notes whether the three-slot form would have held the pair: the host's choice for the next align)
+			if (T == 512 && K == 4 && R.n_snap == 0 && gb - ga + 3 > 23) {
+				if (((hi < cmax ? hi + 1 : cmax) >> 8) - gl_next + 1 > 23) R.n_snap = 1;
+				hold = false;
+			}
+			// (biased offsets, sequences beyond 32 kb: the room arithmetic holds ql - d in 16 unsigned bits; lo >= 256 ga for as long as the key holds)
+			if (BI) {
+				if (cmax - lo > 65535) { R.status = ST_BAND_OVERFLOW; return true; }
+				if (cmax - (ga << 8) > 65535) hold = false;
+			}
+			const int32_t gspan = gb - ga;
+			int n_busy = 0;
+			st = 0;
+#pragma unroll
+			for (int k = 0; k < K; ++k) {
+				// a chunk that left the window: its columns are not computed any more, i.e. their E/F are dead.  It runs through the ordinary
+				// code D more times (every column outside the window: masked dead — rare, a window edge crosses a chunk boundary inwards only
+				// at a shrink), which ages the slot's registers and edge-table entries; after that there is nothing left to do.
+				if ((uint32_t)(gk[k] - ga) <= (uint32_t)gspan) {
+					idle[k] = 0;
+					st |= (1u | (gk[k] == ga ? 2u : 0u) | (gk[k] == gb ? 4u : 0u)) << (4 * k);
+					if (k < 2 || k == K - 1) ++n_busy;
+				} else if (idle[k] < kAgeOut) {
+					++idle[k];
+					st |= 9u << (4 * k);
+					hold = false;
+				}
+			}
+			// the waves with the most chunks to do set the pace of the penalty: let them issue first.  Chunks are dealt round-robin from
+			// chunk ga on: the wave at distance p from it holds ceil((n - p) / NW) of the n active chunks.
+			// One priority level per active chunk of the wave (0 ... 3), kept through the barrier and the next header: 18.4 -> 17.7 ms on
+			// 1024 x 10 kb against "two or more chunks: 3, else 0"; stepping it down as chunks complete 19.1, other maps 17.8 ... 18.3, one more
+			// level for a wave that walked a long run at the last penalty: no change.
+			if ((NW & (NW - 1)) == 0) {
+				// this wave holds ceil(left / NW) chunks; the waves that hold the window's first or last chunk (masks, liveness) count one more (17.7 -> 17.45 ms)
+				const int32_t pos = (wave - ga) & (NW - 1);
+				const int32_t left = gspan + 1 - pos + ((pos == 0 || ((gb - wave) & (NW - 1)) == 0) ? NW : 0);
+				if (left > 2 * NW) __builtin_amdgcn_s_setprio(3);
+				else if (left > NW) __builtin_amdgcn_s_setprio(2);
+				else if (left > 0) __builtin_amdgcn_s_setprio(1);
+				else __builtin_amdgcn_s_setprio(0);
+			} else {
+				if (n_busy >= 3) __builtin_amdgcn_s_setprio(3);
+				else if (n_busy == 2) __builtin_amdgcn_s_setprio(2);
+				else if (n_busy == 1) __builtin_amdgcn_s_setprio(1);
+				else __builtin_amdgcn_s_setprio(0);
+			}
+			// every row must read as dead next to the chunks it was computed for: which wave stores them (the waves next to the window's ends hold the fewest chunks)
+			if (ga >= 1 && wave == (ga - 1) % NW) st |= 1u << 24;
+			if (wave == (gb + 1) % NW) st |= 1u << 25;
+			est = st, ekey = kEpoch && hold ? ~key : -1; // (negative: this penalty ran the full header; the bookkeeping behind the barrier turns ~key into key unless the mapping moves)
+		}
 		const char *const rowx = Hb + bx, *const row1 = Hb + b1, *const row2 = Hb + b2;
 		char *const rown = Hb + bn;
 		const bool track_good = (((256 - (s_new & 255)) & 255) < nH); // a shrink can still see this slice
@@ -467,7 +543,6 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			if (k == K - 1 && wave == NW - 1) *(int2*)(lds2 + wE - (NW - 1) * 16) = make_int2(e1b, e2b);  // slot NWK-1 is slot 0's left neighbour
 			if (k == 0 && wave == 0) *(int2*)(lds2 + wF + (NWK + 1) * 16 + 8) = make_int2(f1a, f2a);       // slot 0 is slot NWK-1's right neighbour
 		};
-		const int32_t ga = lo >> 8, gb = hi >> 8, gspan = gb - ga; // chunks [ga, gb] meet the window
 		// (not in the widest geometry: what it hands back goes to the generic kernel, several times slower — it would only do so at penalty 1024
 		// and beyond 1.5 x its span, and the bookkeeping costs the headline kernel 21 more spilled SGPRs)
 		// (the span geometry forecasts later: what it hands back goes to the generic kernel, twice as slow — no more)
@@ -486,38 +561,20 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 #endif
 		}
 
-		bool act[K];
+		if (!kEpoch) { // (the gated geometries: activity and priority where the full header always had them, behind wave 0's stores)
 #pragma unroll
-		for (int k = 0; k < K; ++k) act[k] = (uint32_t)(gk[k] - ga) <= (uint32_t)gspan;
-		// the waves with the most chunks to do set the pace of the penalty: let them issue first.  Chunks are dealt round-robin from
-		// chunk ga on: the wave at distance p from it holds ceil((n - p) / NW) of the n active chunks.
-		bool busy;
-		if ((NW & (NW - 1)) == 0) busy = ((wave - ga) & (NW - 1)) < gspan + 1 - NW;
-		else busy = (int)act[0] + (int)act[1] + (K > 2 ? (int)act[K - 1] : 0) >= 2;
-		// One priority level per active chunk of the wave (0 ... 3), kept through the barrier and the next header: 18.4 -> 17.7 ms on
-		// 1024 x 10 kb against "two or more chunks: 3, else 0"; stepping it down as chunks complete 19.1, other maps 17.8 ... 18.3, one more
-		// level for a wave that walked a long run at the last penalty: no change.
-		if ((NW & (NW - 1)) == 0) {
-			// this wave holds ceil(left / NW) chunks; the waves that hold the window's first or last chunk (masks, liveness) count one more (17.7 -> 17.45 ms)
+			for (int k = 0; k < K; ++k) act[k] = (uint32_t)(gk[k] - ga) <= (uint32_t)(gb - ga);
 			const int32_t pos = (wave - ga) & (NW - 1);
-			const int32_t left = gspan + 1 - pos + ((pos == 0 || ((gb - wave) & (NW - 1)) == 0) ? NW : 0);
+			const int32_t left = gb - ga + 1 - pos + ((pos == 0 || ((gb - wave) & (NW - 1)) == 0) ? NW : 0);
 			if (left > 2 * NW) __builtin_amdgcn_s_setprio(3);
 			else if (left > NW) __builtin_amdgcn_s_setprio(2);
 			else if (left > 0) __builtin_amdgcn_s_setprio(1);
 			else __builtin_amdgcn_s_setprio(0);
-			(void)busy;
-		} else {
-			const int n_busy = (int)act[0] + (int)act[1] + (K > 2 ? (int)act[K - 1] : 0);
-			if (n_busy >= 3) __builtin_amdgcn_s_setprio(3);
-			else if (n_busy == 2) __builtin_amdgcn_s_setprio(2);
-			else if (n_busy == 1) __builtin_amdgcn_s_setprio(1);
-			else __builtin_amdgcn_s_setprio(0);
-			(void)busy;
 		}
 #ifdef MWF_B2_TIMING
 		int n_act = 0;
 #pragma unroll
-		for (int k = 0; k < K; ++k) n_act += act[k] ? 1 : 0;
+		for (int k = 0; k < K; ++k) n_act += (kEpoch ? (st >> (4 * k) & 9u) == 1u : act[k]) ? 1 : 0;
 #endif
 
 #ifdef MWF_B2_TIMING
@@ -527,21 +584,24 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		// ---- every row must read as dead next to the chunks it was computed for (a later window reaches at most nH + 1 columns
 		// beyond this one: the reference's pads, miniwfa.c:96-99); the waves next to the window's ends hold the fewest chunks.  These
 		// stores go first: the store that may stay in flight across the barrier (relaxed_stores) is then a chunk's own.
-		if (ga >= 1 && wave == (ga - 1) % NW) *(int2*)(rown + ((uint32_t)((ga - 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
-		if (wave == (gb + 1) % NW) *(int2*)(rown + ((uint32_t)((gb + 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
+		// (who stores them is part of the slot state; the row is new each penalty)
+		if (kEpoch ? (st & (1u << 24)) != 0 : (ga >= 1 && wave == (ga - 1) % NW)) *(int2*)(rown + ((uint32_t)((ga - 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
+		if (kEpoch ? (st & (1u << 25)) != 0 : wave == (gb + 1) % NW) *(int2*)(rown + ((uint32_t)((gb + 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
 #if MWF_B2_TIMING == 2
 		bool chunk_timed = false;
 		uint32_t ct[4] = {0, 0, 0, 0};
 #endif
 #pragma unroll
 		for (int k = 0; k < K; ++k) {
-			// a chunk that left the window: its columns are not computed any more, i.e. their E/F are dead.  It runs through the ordinary
-			// code D more times (every column outside the window: masked dead — rare, a window edge crosses a chunk boundary inwards only
-			// at a shrink), which ages the slot's registers and edge-table entries; after that there is nothing left to do.
-			if (!act[k]) {
+			// the slot's class: one bit test and one branch for a slot with nothing to do; an ageing slot runs through the ordinary code
+			const uint32_t cls = st >> (4 * k);
+			if (kEpoch) {
+				if (!(cls & 1u)) continue; // uniform
+			} else if (!act[k]) {
 				if (idle[k] >= kAgeOut) continue; // uniform
 				++idle[k];
 			} else idle[k] = 0;
+			const bool edgy = (cls & 0xeu) != 0; // uniform: holds a window edge or lies outside the window — every other running chunk is interior, ga < g < gb
 			// (the window bounds are laundered per slot: what the chunk code derives from them stays inside this branch instead of being
 			// computed up front by waves that hold no active chunk)
 			int32_t lo = uni(lo_p), hi = uni(hi_p);
@@ -562,7 +622,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// slot's outer columns from the edge table
 			const int32_t xE1 = *(const int32_t*)(lds2 + rE1 + k * NW * 16), xE2 = *(const int32_t*)(lds2 + rE2 + k * NW * 16 + 4);
 			const int32_t xF1 = *(const int32_t*)(lds2 + rE1 + (k * NW + 2) * 16 + 8), xF2 = *(const int32_t*)(lds2 + rE2 + (k * NW + 2) * 16 + 12);
-			const bool inside = cb >= lo && cb + kChunk - 1 <= hi; // uniform: every column of the chunk belongs to the window
+			const bool inside = (kEpoch && !edgy) || (cb >= lo && cb + kChunk - 1 <= hi); // uniform: every column of the chunk belongs to the window (an interior chunk's do by definition)
 
 			// ---- recurrence (dev::wf_cell, miniwfa.c:267-278) on pairs of columns
 			const int32_t E1a = e1h[P1][k][0], E1b = e1h[P1][k][1], F1a = f1h[P1][k][0], F1b = f1h[P1][k][1];
@@ -611,7 +671,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// cell, good-bit words, flag word — under the same test as well: no further gain, seven more spilled SGPRs; left as it was.)
 			// (not in the span geometry and the score-only five / six-slot copies on biased offsets: that much slot state leaves no scalar register for the
 			// flag — 1250 x 50 kb +1.6 %, 1024 x 15 kb +1.7 %; with CIGAR the biased copies gain 2 % like the rest)
-			const bool special = is_span(T, K) || (BI4 && !TB) || !inside || g == ga || g == gb || track_good;
+			const bool on_lo = kEpoch ? (cls & 2u) != 0 : g == ga, on_hi = kEpoch ? (cls & 4u) != 0 : g == gb; // uniform
+			const bool special = is_span(T, K) || (BI4 && !TB) || (kEpoch ? edgy : !inside || on_lo || on_hi) || track_good; // (!inside implies edgy)
 			// ---- a chunk that sticks out of the window: the columns outside are not computed by the reference — dead
 			int32_t outA = 0, outB = 0; // 0xffff in the halves of columns outside [lo, hi]
 			uint32_t bits = 0, gbits = 0;
@@ -628,13 +689,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 				nf2A = bfi(outA, kDeadPair, nf2A), nf2B = bfi(outB, kDeadPair, nf2B);
 			}
 			// ---- edge rule (miniwfa.c:325-326): H is the max of the five, so "any live" == "H live"; one lane holds the edge column
-			if (g == ga || g == gb) { // uniform
-				if (g == ga) {
+			if (on_lo || on_hi) { // uniform
+				if (on_lo) {
 					const int32_t rel = lo - cb;
 					const int32_t v = half_of(__builtin_amdgcn_readlane((rel & 1) ? hB : hA, rel >> 2), (rel >> 1) & 1);
 					bits |= v >= -1 - B ? 1u : 0u;
 				}
-				if (g == gb) {
+				if (on_hi) {
 					const int32_t rel = hi - cb;
 					const int32_t v = half_of(__builtin_amdgcn_readlane((rel & 1) ? hB : hA, rel >> 2), (rel >> 1) & 1);
 					bits |= v >= -1 - B ? 2u : 0u;
@@ -873,11 +934,15 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		// they age (and, FOLD, fold the rows they computed) in place.  A slot that wrapped while it aged would run the chunk NWK further up
 		// through the ordinary code, and that chunk's dead stores may lie beyond the end of the row (found by profiles/fuzz_fold.py: a
 		// 2.3 kb unrelated pair on four slots lost cells of the NEXT row that way — n_iter off by 82).
-		if (gl_next < gl) gl = gl_next, remap(gl), up_wait = 0;
-		else if (gl_next > gl) {
-			up_min = up_wait == 0 ? gl_next : min(up_min, gl_next);
-			if (++up_wait > kAgeOut) gl = up_min, remap(gl), up_wait = 0;
-		} else up_wait = 0;
+		// (a penalty that took the fast header has gl_next == gl and up_wait == 0: the key, which is not negative then, says so.  A mapping that moves, or waits to, drops the key.)
+		if (!kEpoch || ekey < 0) {
+			if (gl_next < gl) gl = gl_next, remap(gl), up_wait = 0, ekey = 0;
+			else if (gl_next > gl) {
+				up_min = up_wait == 0 ? gl_next : min(up_min, gl_next);
+				if (++up_wait > kAgeOut) gl = up_min, remap(gl), up_wait = 0;
+				ekey = 0;
+			} else up_wait = 0, ekey = ~ekey; // (-1, nothing to keep, becomes 0: no key)
+		}
 		if (TB) tb_used += row_bytes;
 		if ((s & 0xff) == 0) { // shrink (reference wf_stripe_shrink, miniwfa.c:144-171) on the interleaved good bits
 			if (tid == 0) sh.red[0] = 0x7fffffff, sh.red[1] = -1;
