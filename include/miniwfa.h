@@ -260,6 +260,8 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
  *   "div_aware"         1 (default): the size classes follow the batch's divergence (an 8-mer sketch of a few pairs: on the host while a batch is packed, on the device when one is wrapped); 0: lengths only
  *   "dev_retry"         1 (default): what the short-pair kernel hands back is re-run from a device-side list by a follow-up launch; 0: through the host
  *   "band_fold"         1 (default): score-only with o1 == x the packed kernel folds the gap-open row into its E1 / F1 registers (one row load less per chunk); 0: never
+ *   "probe_table"       1 (default): the 512-thread packed kernel, default gap extensions, folded form, takes the first probe of its match extension from per-position 8-mer
+ *                       tables in LDS (2 bytes per base of target + query) while two workgroups still share a CU; 0: never
  *   "trim"              (action) free the engine's workspace pools; they grow back on demand.
  * (The hooks tests and profiling scripts force kernels, geometries and failure paths with — "force_kind", "block", "sys_c" ... — are a separate, undeclared entry point,
  * mwf_gpu_test_hook in csrc/mwf_engine.cpp.) */

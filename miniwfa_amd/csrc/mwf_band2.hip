@@ -49,6 +49,16 @@ constexpr int kWideWaves = 4; // waves per SIMD the widest geometry is compiled 
 constexpr int kChunk = 256;
 constexpr int kFoldMaxLag = 8; // largest o1 + e1 the folded form of the packed kernel is launched for
 constexpr int32_t kDeadPair = (int32_t)0x80008000u;
+// The table form (mwf_band2_tab.hip includes this file with MWF_BAND2_TAB set): the first probe of the match extension reads one halfword per sequence and
+// column from a table of 8-mers (build_probe_table) instead of shifting sixteen bases out of two dwords of the 2-bit copy.  The kernel carries a name of its own.
+#ifdef MWF_BAND2_TAB
+constexpr bool kTabProbe = true;
+#define MWF_BAND2_KERNEL wfa_band2_tab_kernel
+#else
+constexpr bool kTabProbe = false;
+#define MWF_BAND2_KERNEL wfa_band2_kernel
+#endif
+constexpr int kTabSlack = 258; // table entries beyond tl + ql: target position tl, query position -1, and the query positions a chunk's columns beyond cmax clamp to (up to ql + 255)
 
 __device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
@@ -143,14 +153,14 @@ __device__ __forceinline__ int32_t probe16_count(const Probe16 &p, int32_t j, in
 }
 // exact-match run t[j..] == q[iq..] on the 2-bit copies, at most `room`, the first n0 known equal, walked by all 64 lanes:
 // 1024 bases per trip.  Arguments wave-uniform.
-__device__ __forceinline__ int32_t run_wave16(int32_t qbase, int32_t j, int32_t iq, int32_t room, int32_t n0)
+__device__ __forceinline__ int32_t run_wave16(int32_t qbase, int32_t j, int32_t iq, int32_t room, int32_t n0, int32_t tbase = 0)
 {
 	const int32_t lane = threadIdx.x & 63;
 	int32_t n = n0;
 	while (n < room) {
 		const int32_t off = n + 16 * lane;
 		int32_t m = 0;
-		if (off < room) m = min(min(lead_eq2(seq16(0, j + off) ^ seq16(qbase, iq + off)), 16), room - off);
+		if (off < room) m = min(min(lead_eq2(seq16(tbase, j + off) ^ seq16(qbase, iq + off)), 16), room - off);
 		const unsigned long long stop = __ballot(m < 16);
 		if (stop == 0) { n += 1024; continue; }
 		const int32_t first = (int32_t)__builtin_ctzll(stop);
@@ -192,6 +202,23 @@ __device__ __forceinline__ uint32_t pack2bit(const uint8_t *src, int32_t len, in
 		*(uint32_t*)(lds2 + base + 4 * w) = out;
 	}
 	return bad;
+}
+
+// The table form's probe table, from the 2-bit copies at `tbase` / `qbase` (after pack2bit and a barrier): halfword p <= tl holds the eight bases from target position p
+// (the low 16 bits of seq16), halfword tl + 2 + q those from query position q, -1 <= q <= ql + 255 (zero outside [0, ql]).  The cell of column c at target
+// position j probes halfwords j and j + c + 1: query position j + c - 1 - tl.  Bases behind the end of a sequence are whatever the copy's slack holds — the room clamp
+// of the probe makes them irrelevant.  The table starts at LDS address 0.
+template <int T>
+__device__ __forceinline__ void build_probe_table(int32_t tl, int32_t ql, int32_t tbase, int32_t qbase)
+{
+	const int32_t n = tl + ql + kTabSlack;
+	for (int32_t e = threadIdx.x; e < n; e += T) {
+		const int32_t q = e - tl - 2;
+		uint32_t v = 0;
+		if (e <= tl) v = seq16(tbase, e);
+		else if (q >= 0 && q <= ql) v = seq16(qbase, q);
+		*(uint16_t*)(lds2 + 2 * e) = (uint16_t)v;
+	}
 }
 
 __device__ __forceinline__ uint32_t inm_bit(int32_t d, int32_t k, int32_t tl, int32_t ql)
@@ -300,7 +327,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 {
 	constexpr int NW = T / 64, NWK = NW * K, D = (E1 > E2 ? E1 : E2) + 1;
 	constexpr bool BI = is_span(T, K) || BI4; // biased offsets with range checks (wide_bias): the span geometry and the four-slot 512-thread one's copy for long pairs
-	constexpr int FULL = S2 ? 16 : 8; // bases the first probe of the match extension looks at
+	constexpr bool TAB = kTabProbe && S2; // the first probe reads the 8-mer table in front of the 2-bit copies
+	constexpr int FULL = TAB ? 8 : S2 ? 16 : 8; // bases the first probe of the match extension looks at
 	// FOLD (score-only, gap-open lag - mismatch lag == e1, i.e. o1 == x as in the default penalties): the row a penalty reads for its
 	// mismatch term, H[s-x], IS the row the first gap piece opens from e1 penalties later (miniwfa.c:267-278: both E1 and F1 take
 	// max(H[s-o1-e1], E1/F1[s-e1]) of a neighbouring column).  The registers that hold E1/F1 of the last e1 penalties therefore hold
@@ -372,7 +400,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	}
 	__syncthreads(); // (orders the dead rows before the origin's store)
 	if (tid < 64) { // the origin's run, walked by the first wave
-		const int32_t k0 = (S2 ? run_wave16(qoff, 0, 0, min(tl, ql), 0) : run_wave2(0, qoff, min(tl, ql), 0)) - 1;
+		const int32_t k0 = (S2 ? run_wave16(qoff, 0, 0, min(tl, ql), 0, TAB ? fresh(A).band_lds_tab : 0) : run_wave2(0, qoff, min(tl, ql), 0)) - 1;
 		if (tid == 0) {
 			const int32_t c = tl + 1, e = c & 3;
 			*(int16_t*)(Hb + 8 + (size_t)(uint32_t)(((c & ~3) + ((e & 1) << 1) + (e >> 1)) << 1)) = (int16_t)(k0 - B);
@@ -663,8 +691,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- lane geometry of the chunk: j = k + 1 may reach rj = min(tl, ql - d); query index = j + d, d = c - 1 - tl
 			const int32_t cbp = both16(cb);
 			const int32_t xA = pk_sub(pk_sub(T0, cbp), RA);                  // ql - d of A's columns (garbage beyond cmax, where H is dead)
-			const int32_t rjA = pk_minu(xA, TLp), rjB = pk_minu(pk_sub(xA, ONE), TLp);
-			const int32_t dA = pk_sub(pk_add(RA, cbp), TL1), dB = pk_add(dA, ONE);
+			// (the table form: ql - d clamped at zero, so that a column beyond cmax probes query position d <= ql + 255 — inside the table — and not tl + d.
+			// Both subtractions saturate: a running chunk has cb <= cmax today — hi <= cmax, an ageing slot was in the window once, the remap waits for it to
+			// age out — but the probe's bounds must not rest on that: a chunk beyond cmax gets rj = 0 like a column beyond it, not a wrapped difference)
+			const int32_t xAc = TAB ? pk_subsat(pk_subsat(T0, cbp), RA) : xA;
+			const int32_t rjA = pk_minu(xAc, TLp), rjB = pk_minu(TAB ? pk_subsat(xAc, ONE) : pk_sub(xA, ONE), TLp);
+			// (the table form: the query's table index is j + c + 1, no target length in it)
+			const int32_t dA = TAB ? pk_add(pk_add(RA, cbp), ONE) : pk_sub(pk_add(RA, cbp), TL1), dB = pk_add(dA, ONE);
 			// ---- the rare work in front of the extension — the chunk sticks out of the window, holds a window edge, a shrink is near — behind ONE
 			// uniform test: an interior chunk (most chunks) pays one branch for the three (a uniform branch costs a wave 17-31 cycles,
 			// profiles/r05/branch_rates_microbench.txt): 1024 x 10 kb -2 % score-only, -3 % with CIGAR.  (The rare work behind the extension — end
@@ -750,7 +783,29 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			const int32_t jA = pk_minu(pk_add(hA, ONEB), rjA), jB = pk_minu(pk_add(hB, ONEB), rjB);
 			const int32_t iqA = pk_add(jA, dA), iqB = pk_add(jB, dB);
 			int32_t cnt[4]; // columns c0 (A.lo), c1 (B.lo), c2 (A.hi), c3 (B.hi)
-			if (S2) {
+			if (TAB) {
+				// Eight halfword reads — table entries j and j + c + 1 of the four columns — back to back and waited for once, as below.  A half of the
+				// packed registers becomes a byte address by adding it to itself (SDWA); the table starts at LDS address 0.  j <= rj <= tl and
+				// j + c + 1 <= tl + ql + 257: every address lies inside the table.
+				uint32_t tv[4], qv[4];
+#pragma unroll
+				for (int u = 0; u < 4; ++u) {
+					const uint32_t J = (uint32_t)((u & 1) ? jB : jA), Q = (uint32_t)((u & 1) ? iqB : iqA);
+					uint32_t ta, qa;
+					if (u & 2) {
+						asm("v_add_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" : "=v"(ta) : "v"(J));
+						asm("v_add_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1" : "=v"(qa) : "v"(Q));
+					} else {
+						asm("v_add_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" : "=v"(ta) : "v"(J));
+						asm("v_add_u32_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0" : "=v"(qa) : "v"(Q));
+					}
+					asm volatile("ds_read_u16 %0, %1" : "=v"(tv[u]) : "v"(ta));
+					asm volatile("ds_read_u16 %0, %1" : "=v"(qv[u]) : "v"(qa));
+				}
+				asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]), "+v"(qv[0]), "+v"(qv[1]), "+v"(qv[2]), "+v"(qv[3]));
+#pragma unroll
+				for (int u = 0; u < 4; ++u) asm("v_ffbl_b32 %0, %1" : "=v"(cnt[u]) : "v"(tv[u] ^ qv[u])); // first differing bit, -1 for none: halved after packing (below)
+			} else if (S2) {
 				// Eight LDS reads (two dwords of each sequence for each of the four columns) go out back to back and are waited for ONCE:
 				// left to itself the compiler recycles one register quad and pays four dependent LDS round trips.  Inline asm: the
 				// reads keep their order (volatile), the single wait takes every result as an operand so that no use can move above it.
@@ -793,8 +848,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 				}
 			}
 			typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
-			const int32_t cA = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[0], (uint32_t)cnt[2])); // saturating
-			const int32_t cB = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[1], (uint32_t)cnt[3]));
+			int32_t cA = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[0], (uint32_t)cnt[2])); // saturating
+			int32_t cB = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[1], (uint32_t)cnt[3]));
+			if (TAB) cA = MWF_BC(int32_t, (us2_t)(MWF_BC(us2_t, cA) >> 1)), cB = MWF_BC(int32_t, (us2_t)(MWF_BC(us2_t, cB) >> 1)); // bits -> bases; "no difference" (0xffff) stays above FULL
 #if MWF_B2_TIMING == 2
 			if (timed) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc3) : "v"(cA), "v"(cB) : "memory");
 #endif
@@ -805,6 +861,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- a run of >= FULL matches continues (the cells near the alignment path, and one first probe in 4^FULL by chance).  Each
 			// lane first walks its own runs, four trips at most; what is still open then the whole wave walks.
 			if (__ballot(pendp != 0)) {
+				const int32_t tb0 = TAB ? fresh(A).band_lds_tab : 0; // where the target's 2-bit copy starts
 				int32_t hv[4] = {half_of(hA, 0) + B, half_of(hB, 0) + B, half_of(hA, 1) + B, half_of(hB, 1) + B}; // true offsets
 				int32_t nmat[4] = {(int32_t)((uint32_t)nmA & 0xffffu), (int32_t)((uint32_t)nmB & 0xffffu), (int32_t)((uint32_t)nmA >> 16), (int32_t)((uint32_t)nmB >> 16)};
 				const uint32_t pend = (uint32_t)(((uint32_t)m9A & 0xffffu) > (uint32_t)FULL) | (uint32_t)(((uint32_t)m9B & 0xffffu) > (uint32_t)FULL) << 1 |
@@ -819,7 +876,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 						for (int trip = 0; n < rm; ++trip) {
 							if (trip == 4) { open |= 1u << i; break; }
 							if (S2) {
-								const int32_t m = min(lead_eq2(seq16(0, j + n) ^ seq16(qoff, q + n)), 16);
+								const int32_t m = min(lead_eq2(seq16(tb0, j + n) ^ seq16(qoff, q + n)), 16);
 								n += m;
 								if (m < 16) break;
 							} else {
@@ -840,7 +897,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 						if (!((ob >> i) & 1u)) continue; // uniform
 						const int32_t hh = __builtin_amdgcn_readlane(hv[i], src);
 						const int32_t j = hh + 1, q = c0s + i - 1 - tl + j, rm = min(tl - j, ql - q);
-						const int32_t n = S2 ? run_wave16(qoff, j, q, rm, 80) : run_wave2(j, qoff + q, rm, 40);
+						const int32_t n = S2 ? run_wave16(qoff, j, q, rm, FULL + 64, tb0) : run_wave2(j, qoff + q, rm, 40);
 						nmat[i] = lane == src ? n : nmat[i];
 					}
 				}
@@ -995,7 +1052,7 @@ constexpr int band2_waves(int T, int K, bool TB)
 	return is_span(T, K) ? (T == 1024 ? 4 : 3) : T == 1024 ? 4 : T == kWideT ? kWideWaves : T <= 512 ? ((TB && T < 512) ? 3 : 4) : kWaves768;
 }
 template <int T, int K, int E1, int E2, bool TB, bool S2, bool BI4 = false, bool FOLD = false>
-__global__ __launch_bounds__(T, band2_waves(T, K, TB)) void wfa_band2_kernel(const BatchArgs)
+__global__ __launch_bounds__(T, band2_waves(T, K, TB)) void MWF_BAND2_KERNEL(const BatchArgs)
 {
 	constexpr int NWK = (T / 64) * K, D = (E1 > E2 ? E1 : E2) + 1;
 	// the arguments are read from the kernarg segment where they are used (dev::kernel_args / dev::fresh), never held for the kernel's lifetime
@@ -1024,16 +1081,22 @@ __global__ __launch_bounds__(T, band2_waves(T, K, TB)) void wfa_band2_kernel(con
 		const int32_t pair = A.order ? A.order[item] : item;
 		PairMem M;
 		pair_mem(A, (int32_t)blockIdx.x, pair, M);
-		const int32_t qoff = S2 ? ((M.tl >> 4) + 2) * 4 : ((M.tl + 3) & ~3) + 8; // both sequences start on a dword
+		constexpr bool TAB = kTabProbe && S2;
+		const int32_t toff = TAB ? A.band_lds_tab : 0; // (the table form: the probe table comes first, the 2-bit copies behind it)
+		const int32_t qoff = toff + (S2 ? ((M.tl >> 4) + 2) * 4 : ((M.tl + 3) & ~3) + 8); // both sequences start on a dword
 		PassResult R;
 		R.status = ST_OK, R.s = 0, R.info = 0, R.n_snap = 0, R.cells = 0;
 		if (S2) {
-			uint32_t bad = pack2bit<T>(M.ts, M.tl, 0);
+			uint32_t bad = pack2bit<T>(M.ts, M.tl, toff);
 			bad |= pack2bit<T>(M.qs, M.ql, qoff);
 			// a base other than A/C/G/T: the host re-runs the pair on the byte-wise copy of this kernel
 			if (bad) sh.word[2] = 1;
 			__syncthreads();
 			if (uni(sh.word[2])) R.status = ST_ALPHABET;
+			if (TAB) { // (read only behind the barriers in front of the first penalty)
+				if (2 * (M.tl + M.ql + kTabSlack) > toff) R.status = ST_BAND_OVERFLOW; // (the host sizes the table for the launch's longest pair)
+				else if (R.status == ST_OK) build_probe_table<T>(M.tl, M.ql, toff, qoff);
+			}
 		} else {
 			for (int32_t j = threadIdx.x; j < M.tl; j += T) lds2[j] = M.ts[j];
 			for (int32_t j = threadIdx.x; j < M.ql; j += T) lds2[qoff + j] = M.qs[j];
@@ -1043,7 +1106,7 @@ __global__ __launch_bounds__(T, band2_waves(T, K, TB)) void wfa_band2_kernel(con
 		if (R.status == ST_OK) R = band2_pass<T, K, E1, E2, TB, S2, BI4, FOLD>(A, M, sh, edge_base, qoff, trace);
 		if (T == 512 && K == 4 && R.n_snap && threadIdx.x == 0 && fresh(A0).report_wide) atomicOr((unsigned int*)(fresh(A0).cig_head + 1), 1u); // (mwf_plan.cpp: PlanCache::wide_state)
 		R.n_snap = 0;
-		if (S2) M.t2 = lds2, M.q2 = lds2 + qoff; // the traceback's back-match reads the 2-bit copies in LDS
+		if (S2) M.t2 = lds2 + toff, M.q2 = lds2 + qoff; // the traceback's back-match reads the 2-bit copies in LDS
 		if (TB && FOLD) M.tb_fwd = 1;
 		finish_pair(fresh(A0), M, (int32_t)blockIdx.x, pair, R, R.status, 0, T <= 256 ? &cig_loc : nullptr); // (block mode: the geometries of the short pairs — thousands per launch)
 	}
@@ -1063,13 +1126,13 @@ void launch_variant(const BatchArgs &a, int grid, int lds, hipStream_t st)
 	}
 	// the attribute is per device and this may run on several host threads (mwf_wfa_batch_multi): set it on every launch that needs it
 	if (lds > 48 * 1024) {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&MWF_BAND2_KERNEL<T, K, E1, E2, TB, S2, BI4, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 		(void)hipGetLastError();
 	}
 	// diagnostics: which instantiation this launch is — the eight template arguments, as tests/band_matrix.py lists them — and how many pairs it was given
 	if (getenv("MWF_DEBUG"))
 		fprintf(stderr, "[libmwf_hip] band2 launch: T %d K %d E1 %d E2 %d TB %d S2 %d BI4 %d FOLD %d, %d pairs, grid %d\n", T, K, E1, E2, (int)TB, (int)S2, (int)BI4, (int)FOLD, (int)a.n_pairs, grid);
-	hipLaunchKernelGGL((wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), dim3(grid), dim3(T), lds, st, a);
+	hipLaunchKernelGGL((MWF_BAND2_KERNEL<T, K, E1, E2, TB, S2, BI4, FOLD>), dim3(grid), dim3(T), lds, st, a);
 }
 
 template <int T, int K, int E1, int E2, bool BI4 = false>
@@ -1102,16 +1165,16 @@ int occ_one(int lds_seq, bool seq2, bool tb)
 	hipError_t e;
 	if constexpr (is_span(T, K) || (T == 512 && K >= 4)) {
 		if (!seq2) return 0;
-		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, true, true, BI4>, T, lds)
-		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, false, true, BI4>, T, lds);
+		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, true, true, BI4>, T, lds)
+		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, false, true, BI4>, T, lds);
 	} else if constexpr (T == 768) {
 		if (seq2) return 0;
-		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, true, false>, T, lds)
-		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, false, false>, T, lds);
+		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, true, false>, T, lds)
+		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, false, false>, T, lds);
 	} else {
 		if (!seq2) return 0;
-		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, true, true>, T, lds)
-		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_band2_kernel<T, K, E1, E2, false, true>, T, lds);
+		e = tb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, true, true>, T, lds)
+		       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, E1, E2, false, true>, T, lds);
 	}
 	return e == hipSuccess ? n : 0;
 }
@@ -1124,6 +1187,8 @@ int occ_one(int lds_seq, bool seq2, bool tb)
 // Those copies (class 14 of mwf_plan.cpp) for every set but (2, 1) live in two further units, mwf_band2_bi.hip — (2,2), folded and not, and (1,1) — and
 // mwf_band2_bi_deep.hip — (3,1), (3,2), (4,1) —, which include this file with MWF_BAND2_BIASED set to 1 / 2 and hold launch_band2_bi1 / _bi2, band2_occupancy_bi1 / _bi2
 // and nothing else; (2, 1)'s stay in this unit.
+// The table form of the first probe (kTabProbe) is a sixth unit, mwf_band2_tab.hip, which includes this file with MWF_BAND2_TAB set: wfa_band2_tab_kernel on 512 x 3 and
+// 512 x 4, (2,1), 2-bit copies, folded, with and without traceback, and launch_band2_tab / band2_occupancy_tab.
 // (4,2) is not built: its 10 kb batches run on the span geometry (e2 == 2: the worst-case penalty does not fit plain 16-bit offsets), where 24 history registers
 // per slot spill ~100 VGPRs, and gained 1.17 x / 1.13 x over the generic kernel — below what its code is worth.
 #define MWF_BAND2_CAT_(a, b) a##b
@@ -1136,8 +1201,11 @@ int launch_band2_bi1(const BatchArgs &a, int grid, const BandGeom &g, void *stre
 int launch_band2_bi2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int band2_occupancy_bi1(const Penalty &p, const BandGeom &g, bool cigar);
 int band2_occupancy_bi2(const Penalty &p, const BandGeom &g, bool cigar);
+int launch_band2_tab(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar);
+bool band2_tab_supported(const Penalty &p, bool band_fold);
 
-#if !defined(MWF_BAND2_DEEP) && !defined(MWF_BAND2_BIASED)
+#if !defined(MWF_BAND2_DEEP) && !defined(MWF_BAND2_BIASED) && !defined(MWF_BAND2_TAB)
 // the packed kernel: (e1,e2) instantiated, sequences fit LDS (the host checks), every H lag >= 1
 bool band2_supported(const Penalty &p)
 {
@@ -1219,7 +1287,63 @@ bool band2_supported(const Penalty &p)
 		MWF_BAND2_REST(FN, __VA_ARGS__)                                             \
 	} while (0)
 
-#if defined(MWF_BAND2_BIASED)
+#if defined(MWF_BAND2_TAB)
+// the table form: 512 threads x 3 / 4 slots, (2,1), 2-bit copies, folded (the host asks for nothing else: choose_kernel, BandGeom::tab)
+namespace {
+bool tab_geom_ok(const Penalty &p, const BandGeom &g)
+{
+	return g.packed == 1 && g.block == 512 && g.seq2 != 0 && g.tab > 0 && g.tab % 16 == 0 && g.lds_bytes > g.tab && band2_tab_supported(p, true);
+}
+template <int K, bool TB>
+int launch_tab(const BatchArgs &a, int grid, int lds, hipStream_t st)
+{
+	if (lds > 48 * 1024) {
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&MWF_BAND2_KERNEL<512, K, 2, 1, TB, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		(void)hipGetLastError();
+	}
+	// diagnostics: the record of launch_variant unchanged, then a line of this form's own
+	if (getenv("MWF_DEBUG")) {
+		fprintf(stderr, "[libmwf_hip] band2 launch: T %d K %d E1 %d E2 %d TB %d S2 %d BI4 %d FOLD %d, %d pairs, grid %d\n", 512, K, 2, 1, (int)TB, 1, 0, 1, (int)a.n_pairs, grid);
+		fprintf(stderr, "[libmwf_hip] band2 table probe: table %d B, lds %d B\n", (int)a.band_lds_tab, lds);
+	}
+	hipLaunchKernelGGL((MWF_BAND2_KERNEL<512, K, 2, 1, TB, true, false, true>), dim3(grid), dim3(512), lds, st, a);
+	return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+template <int K, bool TB>
+int occ_tab(int lds)
+{
+	int n = 0;
+	return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<512, K, 2, 1, TB, true, false, true>, 512, lds) == hipSuccess ? n : 0;
+}
+} // namespace
+
+// the one statement of when the table form applies: its kernels are (2,1), folded — launch_variant's condition for the folded form
+bool band2_tab_supported(const Penalty &p, bool band_fold)
+{
+	return band_fold && p.e1 == 2 && p.e2 == 1 && p.oe1 - p.x == p.e1 && p.oe1 < kFoldMaxLag;
+}
+
+int launch_band2_tab(const BatchArgs &a0, int grid, const BandGeom &g, void *stream)
+{
+	if (!tab_geom_ok(a0.pen, g) || !a0.band_fold) return -1;
+	BatchArgs a = a0;
+	a.band_lds_seq = g.lds_bytes, a.band_lds_tab = g.tab;
+	const bool four = g.span > 512 / 64 * 3 * 256;
+	const int lds = g.lds_bytes + (four ? lds_tail<512, 4, 2, 1>() : lds_tail<512, 3, 2, 1>());
+	hipStream_t st = (hipStream_t)stream;
+	if (four) return a.want_cigar ? launch_tab<4, true>(a, grid, lds, st) : launch_tab<4, false>(a, grid, lds, st);
+	return a.want_cigar ? launch_tab<3, true>(a, grid, lds, st) : launch_tab<3, false>(a, grid, lds, st);
+}
+
+int band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar)
+{
+	if (!tab_geom_ok(p, g)) return 0;
+	const bool four = g.span > 512 / 64 * 3 * 256;
+	const int lds = g.lds_bytes + (four ? lds_tail<512, 4, 2, 1>() : lds_tail<512, 3, 2, 1>());
+	if (four) return cigar ? occ_tab<4, true>(lds) : occ_tab<4, false>(lds);
+	return cigar ? occ_tab<3, true>(lds) : occ_tab<3, false>(lds);
+}
+#elif defined(MWF_BAND2_BIASED)
 int MWF_BAND2_CAT(launch_band2_bi, MWF_BAND2_BIASED)(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
@@ -1252,9 +1376,15 @@ int MWF_BAND2_CAT(band2_occupancy_e, MWF_BAND2_DEEP)(const Penalty &p, const Ban
 	return 0;
 }
 #else
-int launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
+int launch_band2(const BatchArgs &a, int grid, const BandGeom &g0, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
+	BandGeom g = g0;
+	if (g.tab > 0) { // the table form; a geometry it refuses runs the plain form on the same sequence copies
+		const int rc = launch_band2_tab(a, grid, g, stream);
+		if (rc != -1) return rc;
+		g.lds_bytes -= g.tab, g.tab = 0;
+	}
 	if (g.packed == 2 && !(a_e1 == 2 && a_e2 == 1)) return a_e1 <= 2 ? launch_band2_bi1(a, grid, g, stream) : launch_band2_bi2(a, grid, g, stream);
 	if (a_e1 == 3) return launch_band2_e3(a, grid, g, stream);
 	if (a_e1 == 4) return launch_band2_e4(a, grid, g, stream);
@@ -1273,6 +1403,7 @@ bool band2_biased512_supported(const Penalty &p)
 int band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar)
 {
 	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (g.tab > 0) return band2_occupancy_tab(p, g, cigar); // (0 for a geometry the table form refuses: choose_kernel then keeps the plain form)
 	if (g.packed == 2 && !(a_e1 == 2 && a_e2 == 1)) return a_e1 <= 2 ? band2_occupancy_bi1(p, g, cigar) : band2_occupancy_bi2(p, g, cigar);
 	if (a_e1 == 3) return band2_occupancy_e3(p, g, cigar);
 	if (a_e1 == 4) return band2_occupancy_e4(p, g, cigar);

@@ -97,6 +97,7 @@ int mwf_gpu_set(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "div_aware")) g->div_aware = value != 0;
 	else if (!strcmp(name, "dev_retry")) g->dev_retry = value != 0;
 	else if (!strcmp(name, "band_fold")) g->band_fold = value != 0;
+	else if (!strcmp(name, "probe_table")) g->probe_table = value != 0;
 	else if (!strcmp(name, "trim")) { (void)hipSetDevice(g->device); trim(g); }
 	else return -1;
 	++g->tun_gen; // (whatever the tunable: no hand-kept list of "the ones that classify" to forget an entry of)
@@ -116,6 +117,7 @@ int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "lane_chunks") && value >= 0 && value <= 4) g->lane_chunks = (int)value;
 	else if (!strcmp(name, "mid_block") && (value == 0 || value == 256 || value == 512 || value == 1024)) g->mid_block = (int)value;
 	else if (!strcmp(name, "lds_e2")) g->lds_e2 = value != 0;
+	else if (!strcmp(name, "probe_table_lds")) g->probe_table_lds = std::max<int64_t>(0, value);
 	else if (!strcmp(name, "scalar_generic")) g->scalar_generic = value != 0;
 	else if (!strcmp(name, "coop_spin_limit")) g->coop_spin_limit = std::max<int64_t>(0, std::min<int64_t>(value, 0x7fffffff));
 	else if (!strcmp(name, "coop_tb_cap_mb")) g->coop_tb_cap = std::max<int64_t>(1, value) << 20;

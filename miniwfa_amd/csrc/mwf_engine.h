@@ -68,6 +68,8 @@ struct mwf_gpu_s {
 	int retry_mode = 0;         // set around run_batch_kernel(): 1 the launch fills the list, 2 the launch takes its pairs from it
 	int retry_slot = 0;         // ... which of the batch's kRetrySlots lists
 	bool band_fold = true;      // packed band kernel: the folded score-only form where the penalties allow it (o1 == x)
+	bool probe_table = true;    // packed band kernel: the table form of the first probe (mwf_band2_tab.hip) where it applies and two workgroups still share a CU (0: never)
+	int64_t probe_table_lds = 0; // mwf_gpu_test_hook "probe_table_lds": LDS bytes (table + sequence copies) above which a launch keeps the plain form (0: 74 KB, choose_kernel) — tests of the fall-back
 	bool div_aware = true;      // weigh the size classes' length limits by the batch's estimated divergence (batches built from host memory)
 	int64_t tun_gen = 0;        // bumped by every successful mwf_gpu_set(): a cached plan of an align (PlanCache) is only replayed under the tunables it was made under
 	int64_t coop_min_len = 0;

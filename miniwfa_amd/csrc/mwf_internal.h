@@ -135,6 +135,7 @@ struct BatchArgs {
 	int32_t sys_coop_launch;   // host side only: 1 = launch through hipLaunchCooperativeKernel (the runtime then guarantees that every workgroup is resident)
 	int64_t *timeline;         // packed band kernel, profiles only (null otherwise): [pair][4] wall clock (100 MHz) when its workgroup took it and when it was
 	                           // done, the CU (__smid) and the workgroup — one record per pair, never per penalty (mwf_gpu_test_hook "timeline")
+	int32_t band_lds_tab;      // packed band kernel, table form (mwf_band2_tab.hip): bytes of the probe table in front of the sequence copy (part of band_lds_seq)
 };
 
 // launch wrappers implemented in mwf_kernels.hip (generic kernel: any penalties, any band, low-memory mode)
@@ -175,6 +176,7 @@ struct BandGeom {
 	int seq2;         // packed kernel: the sequence copy holds 2 bits per base (pairs of plain A/C/G/T; others come back as ST_ALPHABET)
 	int lane;         // 1: the one-wave, one-diagonal-per-lane kernel for short pairs (mwf_lane.hip): block 64, span 64, lds_bytes = rings + sequences;
 	                  // 2: the one-workgroup, one-diagonal-per-lane kernel for a few mid-size pairs (mwf_mid.hip): span = columns of its LDS rows
+	int tab;          // packed kernel, table form (mwf_band2_tab.hip): bytes of lds_bytes that hold the probe table (0: the first probe reads the 2-bit copy)
 };
 // one pair (or a few) across the whole device: mwf_sys.hip (the per-penalty hand-off kernel of rounds 1-2, mwf_coop.hip, was removed in round 5)
 bool coop_supported(const Penalty &p);
@@ -211,6 +213,7 @@ int  launch_mid(const BatchArgs &a, int grid, int block, int lds, bool seq2, voi
 bool band2_supported(const Penalty &p);
 int  launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar);
+bool band2_tab_supported(const Penalty &p, bool band_fold); // the table form of the first probe (mwf_band2_tab.hip, BandGeom::tab) has kernels for these penalties
 bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for the set: every set band2_supported takes
 int  band2_biased512_chunks();                       // ... and the 512-thread geometry's copy on biased offsets (8 waves x slots per wave)
 int  band2_span_chunks();                            // 256-column chunks its 1024-thread geometry holds (16 waves x slots per wave)

@@ -128,7 +128,7 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	// takes the class that fits that, not the one that fits the worst case)
 	const int64_t max_window = window_hint > 0 ? std::min<int64_t>(std::min<int64_t>(max_len + 1, 2 * max_bound + 3), window_hint) : std::min<int64_t>(max_len + 1, 2 * max_bound + 3);
 	BandGeom bg;
-	bg.packed = 0, bg.seq2 = 0, bg.lane = 0;
+	bg.packed = 0, bg.seq2 = 0, bg.lane = 0, bg.tab = 0;
 	// Packed variants (E/F registers as int16 pairs): valid when no offset (a target index, plus at most one per penalty for
 	// offsets that ran past the matrix) and no penalty count can reach 32767.  They halve the state registers, which is
 	// what lets several workgroups share a CU — one pair's barrier phase then overlaps another's compute:
@@ -152,7 +152,8 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	// geometry picked by the caller for a size class (pairs short enough that their window should stay inside a small span)
 	if (g->block == 0 && (geom_block == 64 || geom_block == 128 || geom_block == 256)) bg.block = geom_block;
 	bg.span = bg.block / 64 * (bg.block != 768 ? 3 : 2) * 256;
-	const bool four_slots = bg.block == 512 && g->block == 0 && window_hint > kBandWideWindow && window_hint <= kBandWide4Window;
+	// (a forced 512-thread block with "wide_slots" 4: four slots whatever the window — tests of the four-slot kernels on short pairs)
+	const bool four_slots = bg.block == 512 && ((g->block == 0 && window_hint > kBandWideWindow && window_hint <= kBandWide4Window) || (g->block == 512 && g->wide_slots == 4));
 	if (four_slots) bg.span = 512 / 64 * 4 * 256;
 	if (want_kind != 2 && max_len + 1 > 4 * (int64_t)bg.span) return; // windows will mostly outgrow the span: go generic at once
 	const int64_t lds_cap = bg.block >= 768 ? 140 * 1024 : bg.block >= 512 ? 70 * 1024 : bg.block == 256 ? 36 * 1024 : bg.block == 128 ? 18 * 1024 : 9 * 1024;
@@ -174,6 +175,19 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	}
 	if (bg.lds_bytes == 0) return; // the packed kernel keeps the sequences in LDS: what does not fit takes the generic kernel
 	pl.kind = 2, pl.band = bg;
+	// The table form (mwf_band2_tab.hip): the 512-thread geometry on 2-bit copies, default gap extensions, folded — the first probe of the match extension reads
+	// per-position 8-mer tables, one halfword per base of target and query (plus 258 entries of slack) in front of the 2-bit copies.  Worth its LDS only while two
+	// workgroups share a CU: the kernel is asked with the launch's real LDS size (a 10 kb pair: 40.7 KB of table + 5 KB of copies + 5.2 KB of bookkeeping words and edge table); otherwise the plain form, wfa_band2_kernel.
+	// (the budget only spares the query: a CU's 160 KB over two workgroups, less 6 KB for the bookkeeping words and the edge table — 5.2 KB on four slots; cached_occupancy decides)
+	if (g->probe_table && bg.block == 512 && bg.seq2 && band2_tab_supported(P, g->band_fold)) {
+		const int64_t tab = (2 * (max_len + 258) + 15) / 16 * 16;
+		const int64_t budget = g->probe_table_lds > 0 ? g->probe_table_lds : (160 / 2 - 6) * 1024;
+		if (tab + bg.lds_bytes <= budget) {
+			pl.band.tab = (int)tab, pl.band.lds_bytes = (int)(tab + bg.lds_bytes);
+			pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
+			if (cached_occupancy(g, P, pl, 0, false) < 2) pl.band = bg;
+		}
+	}
 }
 
 // resident workgroups per CU of a kernel variant (one runtime query per variant and engine)
@@ -182,7 +196,7 @@ int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_
 	uint64_t key;
 	if (pl.kind == 2)
 		key = 1ull | (uint64_t)pl.band.block << 4 | (uint64_t)(pl.band.packed == 1) << 16 | (uint64_t)(pl.band.packed == 2) << 15 | (uint64_t)(pl.band.lds_bytes > 0) << 17 | (uint64_t)pl.cigar << 18 |
-		      (uint64_t)(pl.band.seq2 != 0) << 3 | (uint64_t)(pl.band.lane == 1) << 2 | (uint64_t)(pl.band.block == 512 && pl.band.span > 6144) << 1 | (uint64_t)(pl.band.block == 512 ? pl.band.span / 2048 : 0) << 56 | (uint64_t)(pl.band.lane == 2) << 19 | (uint64_t)P.e1 << 20 | (uint64_t)P.e2 << 28 | (uint64_t)pl.band.lds_bytes << 36;
+		      (uint64_t)(pl.band.seq2 != 0) << 3 | (uint64_t)(pl.band.lane == 1) << 2 | (uint64_t)(pl.band.block == 512 && pl.band.span > 6144) << 1 | (uint64_t)(pl.band.block == 512 ? pl.band.span / 2048 : 0) << 56 | (uint64_t)(pl.band.lane == 2) << 19 | (uint64_t)P.e1 << 20 | (uint64_t)P.e2 << 28 | (uint64_t)pl.band.lds_bytes << 36 | (uint64_t)(pl.band.tab > 0) << 62;
 	else key = 2ull | (uint64_t)pl.block << 4 | (uint64_t)stream_pass << 16 | (uint64_t)ring16 << 17 | (uint64_t)(P.nH > kMaxRing) << 18 | (uint64_t)lds_e2_cols << 20;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;

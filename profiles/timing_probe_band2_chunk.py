@@ -9,6 +9,7 @@ import ctypes as C
 from miniwfa_amd.synth import synth_pair, PackedBatch
 eng = mw.Engine(0)
 if len(sys.argv) > 1: eng.set("band_fold", int(sys.argv[1]))
+if len(sys.argv) > 2: eng.set("probe_table", int(sys.argv[2]))  # 0: the plain first probe on the 2-bit copies, 1 (default): the table form (mwf_band2_tab.hip)
 for n in (1, 512):
     b = eng.upload(PackedBatch([synth_pair(50000, 10000, 0.05)] * n))
     o = mw.opt_init()
