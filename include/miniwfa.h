@@ -60,6 +60,9 @@ void mwf_opt_init(mwf_opt_t *opt);
  * own assert/panic paths): max(x, o1+e1, o2+e2) < 4096 (below 256 every kernel applies; from 256 on — gap-open costs in the
  * hundreds — the pairs run on the generic kernel's big-ring form, one column per lane), and tl+ql < 2^31-4 (columns
  * are 32-bit).  x, e1, e2 >= 1 and o1, o2 >= 0, as the reference requires implicitly (miniwfa.c:390-392).
+ * The fast paths hold sequences at 2 bits per base, which takes pairs of plain upper-case A/C/G/T; with "alpha_remap" (below, or MWF_ALPHA_REMAP=1 for
+ * the calls that create their engines themselves) also any pair with at most four distinct bytes — lower case, U for T, bases coded 0..3.  A pair with
+ * five or more distinct bytes (an N, mixed case) still runs on the byte-wise copies: one geometry of the band kernel, else the generic kernel.
  * Every penalty set gives the reference's answer; which kernels serve it depends on the gap extensions (e1, e2): the whole-device kernel for
  * long pairs ("coop_min_len" below) takes (2,1), (2,2), (1,1) and e1 in {3, 4} with e2 in {1, 2} (minimap2's asm5 / asm20-like sets); under any
  * other pair of extensions long pairs run on the generic one-workgroup-per-pair kernel (about ten times slower on a 150 kb pair).  The packed
@@ -224,6 +227,19 @@ int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int
 /* The summary array and the maps are allocated on first use through the engine's accounting (mwf_gpu_stats_t dev_bytes / dev_bytes_peak
  * include them while the batch lives) and freed with the batch; a caller that never asks pays nothing. */
 
+/* ---- Alphabet classes (kernels: csrc/mwf_alphabet.hip) ---- */
+
+/* The class of one pair by the bytes that occur in target and query together: 0 every byte is one of A C G T (upper case; two empty sequences
+ * included), 1 at most four distinct bytes and not class 0, 2 five or more.  The alignment only needs the equality relation between bytes, so a
+ * class-1 pair can be aligned as a plain one after a bijection of its bytes: the distinct bytes in ascending byte value map to 'A', 'C', 'G', 'T'
+ * in that order.  map (256 bytes; may be NULL): for class 1, map[b] is that letter for every byte b that occurs and 0 for every other; for classes
+ * 0 and 2 all 256 entries are 0.  Needs no device.  Never reads outside ts[0,tl) / qs[0,ql). */
+int32_t mwf_alphabet_class(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256]);
+
+/* Per-pair class (0, 1, 2 as above) of the batch's last align under "alpha_remap" 1, copied to host_out[n].  Fails (negative; mwf_gpu_last_error)
+ * before the first align and when that align ran with the tunable off. */
+int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out);
+
 /* Timing and counters of the most recent mwf_gpu_batch_align on this engine. */
 typedef struct {
 	double  kernel_ms;     /* HIP-event time around the alignment kernels on the engine's stream */
@@ -244,7 +260,7 @@ void mwf_gpu_get_stats(const mwf_gpu_t *g, mwf_gpu_stats_t *st);
  * wavefront slice the core pass opened for `pair`; returns the number of penalties written (<= cap). */
 int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, int32_t pair, int32_t *lohi, int32_t cap);
 
-/* Tunables (call before align; every call invalidates the cached plans of the engine's batches).  Thirteen names and one action:
+/* Tunables (call before align; every call invalidates the cached plans of the engine's batches).  Fifteen names and one action:
  *   "tb_budget_mb"      traceback arena of the one-workgroup-per-pair kernels (0 = automatic: four fifths of what is free, at most a quarter of the device)
  *   "lowmem_budget_mb"  whole-device kernel, opt.step > 0: a first-pass traceback above this many MB switches to the two-pass form whose first pass stores none (0 = a quarter of the device)
  *   "coop_min_len"      tl + ql from which a batch of at most sixteen pairs runs on the whole-device kernel (0 = 20 000 score-only, 15 000 with CIGAR);
@@ -262,6 +278,14 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
  *   "band_fold"         1 (default): score-only with o1 == x the packed kernel folds the gap-open row into its E1 / F1 registers (one row load less per chunk); 0: never
  *   "probe_table"       1 (default): the 512-thread packed kernel, default gap extensions, folded form, takes the first probe of its match extension from per-position 8-mer
  *                       tables in LDS (2 bytes per base of target + query) while two workgroups still share a CU; 0: never
+ *   "alpha_remap"       0 (default): only pairs of plain A/C/G/T take the 2-bit copies.  1: on the first align of an uploaded batch, and on every align of a wrapped one, every pair
+ *                       with at most four distinct bytes (mwf_alphabet_class 1: lower case, RNA, bases coded 0..3) is copied into a per-batch device arena with its bytes mapped onto A/C/G/T
+ *                       and planned and aligned as a plain pair — same s, n_iter and CIGAR; summaries and maps keep reading the original bytes.  A wrapped batch's classes follow its current
+ *                       contents (one small kernel and one wait per align) and pairs of five or more distinct bytes go straight to the byte-wise route.  The arena holds one copy of every such
+ *                       pair (counted in dev_bytes, freed with the batch); if it does not fit what is free the batch runs as with 0.  The drop-in calls read MWF_ALPHA_REMAP=1 instead: the
+ *                       variable is read once per process and applied to an engine when a call creates it, so it must be set before the first such call.  The batch's divergence estimate
+ *                       ("div_aware") is still taken from the original bytes through (byte >> 1) & 3: lower case and U read as their upper-case letters, but codings that collapse under
+ *                       it (bytes 0..3 read as 0, 0, 1, 1) can get other size classes, and so other re-run counts, than the plain twin — never other answers.
  *   "trim"              (action) free the engine's workspace pools; they grow back on demand.
  * (The hooks tests and profiling scripts force kernels, geometries and failure paths with — "force_kind", "block", "sys_c" ... — are a separate, undeclared entry point,
  * mwf_gpu_test_hook in csrc/mwf_engine.cpp.) */

@@ -76,6 +76,7 @@ ABI_SYMBOLS = (
     "mwf_gpu_debug_band",
     "mwf_cigar_summary", "mwf_gpu_batch_dev_cigars", "mwf_gpu_batch_summarize", "mwf_gpu_batch_dev_summary", "mwf_gpu_batch_summary",
     "mwf_gpu_batch_map", "mwf_gpu_batch_dev_map", "mwf_gpu_batch_map_fetch",
+    "mwf_alphabet_class", "mwf_gpu_batch_alphabet",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -171,6 +172,12 @@ def lib() -> C.CDLL:
     L.mwf_gpu_batch_dev_map.restype = C.c_void_p
     L.mwf_gpu_batch_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.mwf_gpu_batch_map_fetch.restype = C.c_int
+    L.mwf_alphabet_class.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p]
+    L.mwf_alphabet_class.restype = C.c_int32
+    L.mwf_gpu_batch_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_alphabet.restype = C.c_int
+    L.mwf_gpu_test_alpha_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    L.mwf_gpu_test_alpha_ms.restype = C.c_int
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
                             ("krealloc", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t]), ("krelocate", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t]),
                             ("kfree", None, [C.c_void_p, C.c_void_p]), ("km_init", C.c_void_p, []), ("km_init2", C.c_void_p, [C.c_void_p, C.c_size_t]),
@@ -326,6 +333,15 @@ def cigar_summary(t: bytes, q: bytes, opt: MwfOpt, cigar: Sequence[int]) -> np.v
     return np.frombuffer(bytes(out), dtype=SUMMARY_DTYPE)[0]
 
 
+def alphabet_class(t: bytes, q: bytes):
+    """mwf_alphabet_class -> (class, map): 0 every byte of the pair is one of A C G T, 1 at most four distinct bytes (and not class 0), 2 five or
+    more.  map: 256 bytes; for class 1 the letter (A, C, G, T by ascending byte value) of every byte that occurs and 0 elsewhere, else all 0 —
+    bytes(t).translate(map) is the pair as "alpha_remap" aligns it.  Needs no device."""
+    m = (C.c_uint8 * 256)()
+    cls = lib().mwf_alphabet_class(len(t), t, len(q), q, m)
+    return int(cls), bytes(m)
+
+
 class Engine:
     """mwf_gpu_t: one device, one stream, one workspace pool."""
 
@@ -360,6 +376,13 @@ class Engine:
         (mwf_gpu_test_hook: forced kernels / geometries / failure paths; exported, not part of the public header)."""
         if lib().mwf_gpu_set(self.h, name.encode(), int(value)) != 0 and lib().mwf_gpu_test_hook(self.h, name.encode(), int(value)) != 0:
             raise ValueError(f"bad tunable {name}={value}")
+
+    def alpha_ms(self):
+        """(classification ms, copy ms) of the mwf_alphabet.hip launches of the engine's last align, from HIP events (test hook; 0.0: not launched)."""
+        ms = (C.c_double * 2)()
+        if lib().mwf_gpu_test_alpha_ms(self.h, ms) != 0:
+            raise RuntimeError("alpha_ms failed: " + self.error())
+        return float(ms[0]), float(ms[1])
 
     def stats(self) -> GpuStats:
         st = GpuStats()
@@ -434,6 +457,15 @@ class Batch:
         if rc < 0:
             raise RuntimeError(f"cigar download failed ({rc}): " + self.eng.error())
         return out[:rc]
+
+    def alphabet(self) -> np.ndarray:
+        """Per-pair alphabet class (int8: 0, 1, 2 as alphabet_class) of the last align under "alpha_remap" 1; raises before the first align and
+        when that align ran with the tunable off (mwf_gpu_batch_alphabet)."""
+        out = np.zeros(max(1, self.n), dtype=np.int8)
+        rc = lib().mwf_gpu_batch_alphabet(self.eng.h, self.h, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"alphabet failed ({rc}): " + self.eng.error())
+        return out[:self.n]
 
     def dev_scores_ptr(self) -> int:
         return lib().mwf_gpu_batch_dev_scores(self.h)

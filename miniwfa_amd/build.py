@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmwf_hip.so")
-SOURCES = ["mwf_band2.hip", "mwf_band2_tab.hip", "mwf_band2_e3.hip", "mwf_band2_e4.hip", "mwf_band2_bi.hip", "mwf_band2_bi_deep.hip", "mwf_kernels.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_sys_deep.hip", "mwf_cigar_ops.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
+SOURCES = ["mwf_band2.hip", "mwf_band2_tab.hip", "mwf_band2_e3.hip", "mwf_band2_e4.hip", "mwf_band2_bi.hip", "mwf_band2_bi_deep.hip", "mwf_kernels.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_sys_deep.hip", "mwf_cigar_ops.hip", "mwf_alphabet.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
 HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
 # sources that include another source: mwf_band2_e3.hip / _e4.hip are mwf_band2.hip again, with only the instantiations for gap extensions of 3 / 4,
 # mwf_band2_bi.hip / _bi_deep.hip with only the 512 x 5 / 512 x 6 copies on biased offsets of every set but (2, 1), mwf_band2_tab.hip with only the table form of the first probe

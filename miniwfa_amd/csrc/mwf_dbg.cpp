@@ -1,9 +1,55 @@
 // mwf_dbg.cpp — CIGAR self-checks of the drop-in ABI (reference mwf-dbg.c:6-31).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "miniwfa.h"
 
+namespace mwf {
+namespace host {
+
+// The alphabet class of one pair (mwf_alphabet_class below; the device twin is mwf_alphabet.hip) from the presence set of its bytes, 256 bits.
+// sym (class 1 only): the distinct bytes in ascending order, the last one repeated up to four.  A pair of five or more distinct bytes is
+// left as soon as a block of 1024 bytes has shown them.  Never reads outside t[0,tl) / q[0,ql).
+int alphabet_scan(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint8_t sym[4])
+{
+	uint64_t m[4] = {0, 0, 0, 0};
+	auto count = [&]() { return __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) + __builtin_popcountll(m[2]) + __builtin_popcountll(m[3]); };
+	for (int side = 0; side < 2; ++side) {
+		const uint8_t *p = side ? q : t;
+		const size_t n = side ? ql : tl;
+		for (size_t at = 0; at < n; at += 1024) {
+			const size_t end = at + 1024 < n ? at + 1024 : n;
+			for (size_t j = at; j < end; ++j) m[p[j] >> 6] |= 1ull << (p[j] & 63u);
+			if (count() > 4) return 2;
+		}
+	}
+	constexpr uint64_t acgt = (1ull << ('A' - 64)) | (1ull << ('C' - 64)) | (1ull << ('G' - 64)) | (1ull << ('T' - 64));
+	if (!m[0] && !m[2] && !m[3] && !(m[1] & ~acgt)) return 0;
+	int have = 0;
+	uint8_t last = 0;
+	for (int k = 0; k < 4; ++k)
+		for (uint64_t w = m[k]; w; w &= w - 1) sym[have++] = last = (uint8_t)(64 * k + __builtin_ctzll(w));
+	for (; have < 4; ++have) sym[have] = last;
+	return 1;
+}
+
+} // namespace host
+} // namespace mwf
+
 extern "C" {
+
+int32_t mwf_alphabet_class(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256])
+{
+	uint8_t sym[4] = {0, 0, 0, 0};
+	const int cls = mwf::host::alphabet_scan((const uint8_t*)ts, tl > 0 ? (size_t)tl : 0, (const uint8_t*)qs, ql > 0 ? (size_t)ql : 0, sym);
+	if (map) {
+		memset(map, 0, 256);
+		if (cls == 1)
+			for (int k = 0; k < 4; ++k)
+				if (k == 0 || sym[k] != sym[k - 1]) map[sym[k]] = (uint8_t)"ACGT"[k];
+	}
+	return cls;
+}
 
 // Penalty and consumed lengths implied by a CIGAR: '='/'X'/'M' advance both sequences, 'I' the
 // query, 'D' the target; an indel run of length L costs min(o1+L*e1, o2+L*e2), 'X' costs x per base.

@@ -72,7 +72,7 @@ void mwf_gpu_destroy(mwf_gpu_t *g)
 	release(g, g->queue);
 	if (g->pin) (void)hipHostFree(g->pin);
 	if (g->res_pin) (void)hipHostFree(g->res_pin);
-	for (hipEvent_t e : {g->ev0, g->ev1, g->pin_ev[0], g->pin_ev[1]})
+	for (hipEvent_t e : {g->ev0, g->ev1, g->pin_ev[0], g->pin_ev[1], g->ev_alpha[0], g->ev_alpha[1], g->ev_alpha[2], g->ev_alpha[3]})
 		if (e) (void)hipEventDestroy(e);
 	if (g->own_stream) (void)hipStreamDestroy(g->stream);
 	delete g;
@@ -98,6 +98,7 @@ int mwf_gpu_set(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "dev_retry")) g->dev_retry = value != 0;
 	else if (!strcmp(name, "band_fold")) g->band_fold = value != 0;
 	else if (!strcmp(name, "probe_table")) g->probe_table = value != 0;
+	else if (!strcmp(name, "alpha_remap") && (value == 0 || value == 1)) g->alpha_remap = (int)value;
 	else if (!strcmp(name, "trim")) { (void)hipSetDevice(g->device); trim(g); }
 	else return -1;
 	++g->tun_gen; // (whatever the tunable: no hand-kept list of "the ones that classify" to forget an entry of)
@@ -125,6 +126,7 @@ int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "sys_p") && sys_p_supported((int)value)) g->sys_p = (int)value; // (8; 4 and 16 only in builds with -DMWF_SYS_ALL_P)
 	else if (!strcmp(name, "sys_c") && (value == 0 || sys_c_supported((int)value))) g->sys_c = (int)value; // (2: builds with -DMWF_SYS_C2 only)
 	else if (!strcmp(name, "work_order") && value >= 0 && value <= 3) g->work_order = (int)value;
+	else if (!strcmp(name, "alpha_arena_budget")) g->alpha_arena_budget = std::max<int64_t>(-1, value); // ("alpha_remap": an arena above this many bytes "does not fit"; -1: ask the device)
 	else if (!strcmp(name, "timeline")) g->timeline = (int64_t*)(intptr_t)value; // (a device array of 4 int64 per pair of every batch aligned while it is set; 0: off)
 	else return -1;
 	++g->tun_gen;
@@ -184,7 +186,7 @@ void mwf_gpu_batch_free(mwf_gpu_batch_t *b)
 	if (g->res_pin_owner == b) g->res_pin_owner = nullptr;
 	give_block(g, g->spare_block, b->block);
 	give_block(g, g->spare_cig, b->cig);
-	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1]}) release(g, *d); // (hipFree waits for a kernel still writing them)
+	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1], &b->alpha_cls, &b->alpha_arena}) release(g, *d); // (hipFree waits for a kernel still writing them)
 	delete b;
 }
 
@@ -346,6 +348,34 @@ int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int
 	return download(g, host_out, b->ops_map[which].p, (size_t)off[b->n] * 4);
 }
 
+/* ------------------------------------------------------------------ alphabet classes ("alpha_remap"; mwf_alphabet.hip, alpha_prepare in mwf_memory.cpp) */
+
+int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out)
+{
+	if (!g || !b || !host_out) return -1;
+	if (!b->aligned) { g->err = "mwf_gpu_batch_alphabet: the batch was not aligned yet (the classes are those of its last align)"; return -2; }
+	if (!b->alpha_known) { g->err = "mwf_gpu_batch_alphabet: the batch's last align ran with \"alpha_remap\" 0 (set it to 1 before the align)"; return -2; }
+	if (b->n > 0) memcpy(host_out, b->h_alpha.data(), (size_t)b->n);
+	return 0;
+}
+
+/* test hook: HIP-event time of the kernels of mwf_alphabet.hip the engine's last align launched: ms[0] the classification, ms[1] the copy (0: not launched).
+   Waits for them.  Exported for tests/ and profiles/, not declared in include/miniwfa.h. */
+int mwf_gpu_test_alpha_ms(mwf_gpu_t *g, double *ms)
+{
+	if (!g || !ms) return -1;
+	(void)hipSetDevice(g->device);
+	for (int k = 0; k < 2; ++k) {
+		float f = 0;
+		ms[k] = 0;
+		if (!g->alpha_timed[k]) continue;
+		HIP_TRY(g, hipEventSynchronize(g->ev_alpha[2 * k + 1]));
+		HIP_TRY(g, hipEventElapsedTime(&f, g->ev_alpha[2 * k], g->ev_alpha[2 * k + 1]));
+		ms[k] = f;
+	}
+	return 0;
+}
+
 /* test hook: trace the band of one pair (columns lo,hi per penalty); returns penalties traced */
 int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, int32_t pair, int32_t *lohi, int32_t cap)
 {
@@ -418,6 +448,9 @@ mwf_gpu_t *acquire_engine(int dev)
 	}
 	mwf_gpu_t *g = mwf_gpu_create(dev, nullptr);
 	if (!g) fatal("cannot open a HIP device; this library has no CPU path", nullptr);
+	// MWF_ALPHA_REMAP=1: the engines the drop-in calls, chain mode and the dispatcher create run with "alpha_remap" 1 (include/miniwfa.h)
+	static const bool alpha = []() { const char *e = getenv("MWF_ALPHA_REMAP"); return e && !strcmp(e, "1"); }();
+	if (alpha) (void)mwf_gpu_set(g, "alpha_remap", 1);
 	return g;
 }
 

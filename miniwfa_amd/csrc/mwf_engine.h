@@ -92,6 +92,8 @@ struct mwf_gpu_s {
 	bool ring16_off_once = false; // set around the re-run of pairs whose offsets outgrew 16 bits
 	int seq2bit = 1;           // packed band kernel: 2-bit sequence copy in LDS for pairs of plain A/C/G/T (0: always bytes)
 	bool acgt_off_once = false; // set around the re-run of pairs that are not plain ACGT
+	int alpha_remap = 0;       // 1: pairs of at most four distinct bytes are copied into a per-batch arena with their bytes mapped onto A/C/G/T and planned as plain pairs (alpha_prepare, mwf_memory.cpp); 0: never
+	int64_t alpha_arena_budget = -1; // mwf_gpu_test_hook "alpha_arena_budget": bytes an arena may take (-1: four fifths of what is free) — tests of the fall-back
 	int lds_e2 = 1;            // generic kernel: keep E2/F2 in LDS where that applies (0: never)
 	int scalar_generic = 0;    // 1: the generic kernel's original one-column-per-lane pass everywhere (comparison / fallback)
 	int64_t coop_spin_limit = 1 << 23; // polls (about a microsecond each) before the whole-device kernel gives up on a workgroup
@@ -117,6 +119,8 @@ struct mwf_gpu_s {
 	bool pin_busy[2] = {false, false}; // a copy out of that half may still be in flight (pin_ev tells)
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	bool ev_pending = false;
+	hipEvent_t ev_alpha[4] = {nullptr, nullptr, nullptr, nullptr}; // around the last align's classification launch [0, 1] and copy launch [2, 3] of mwf_alphabet.hip (created on first use)
+	bool alpha_timed[2] = {false, false};                           // ... which of them that align made
 	mwf_gpu_stats_t stats{};
 	int64_t dev_bytes = 0, dev_bytes_peak = 0; // device memory this engine holds right now / held at most since the last "trim"
 	std::map<uint64_t, int> occ_cache;         // kernel variant -> resident workgroups per CU
@@ -145,6 +149,17 @@ struct mwf_gpu_batch_s {
 	std::vector<int8_t> h_acgt;     // from the host's look at the bytes while a batch is built from host memory: 1 both sequences are plain
 	                                // A/C/G/T, 0 not (such a pair goes to the byte-wise sequence copy at once); empty: unknown (wrapped device
 	                                // buffers — the 2-bit copy finds out on the device and the pair comes back as ST_ALPHABET)
+	// "alpha_remap" (alpha_prepare, mwf_memory.cpp).  While alpha_active, h_acgt is 1 for the pairs of classes 0 and 1 and the align kernels take their
+	// offsets from d_rt_off / d_rq_off: the batch's own for classes 0 and 2, the copy in the arena (as an offset from d_seqs) for class 1.
+	std::vector<int8_t> h_acgt_host; // h_acgt as the upload made it (empty: wrapped) — what h_acgt goes back to
+	std::vector<int8_t> h_alpha;    // class of every pair (mwf_alphabet_class): from the host twin while an uploaded batch was packed, from the kernel's classification at every align of a wrapped one
+	std::vector<uint32_t> h_sym;    // ... and its distinct bytes (AlphabetArgs::sym)
+	DevBuf alpha_cls;               // device: [sym: n uint32 | cls: n int8]
+	DevBuf alpha_arena;             // device: [t_off: n int64 | q_off: n int64 | dst_t, dst_q: the copy launch's destinations, n int64 each | ids of the class-1 pairs: n int32 | 64 bytes | the copies, each sequence on a 16-byte boundary | 64 bytes]
+	const int64_t *d_rt_off = nullptr, *d_rq_off = nullptr;
+	bool alpha_known = false;       // h_alpha describes the last align (mwf_gpu_batch_alphabet)
+	bool alpha_active = false;      // the last align read the copies
+	bool alpha_laid_out = false;    // the arena's offsets (and, uploaded batches, its copies) are in place for h_alpha
 	std::vector<int8_t> h_flags;    // bit 0: runs as high-memory although opt.step > 0 (its penalty bound is below step);
 	                                // bit 1: shared the whole-device kernel with other pairs; bit 2: walk variant of the low-memory mode
 	// results: one region of the block, fetched by one copy
@@ -234,6 +249,8 @@ mwf_gpu_batch_t *batch_common(mwf_gpu_t *g, int32_t n, const int32_t *h_tl, cons
 mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, const char *const *ts, const int32_t *ql, const char *const *qs,
                                  const char *packed, int64_t packed_bytes, const int64_t *p_t_off, const int64_t *p_q_off);
 float estimate_divergence_device(mwf_gpu_t *g, mwf_gpu_batch_t *b);
+int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b); // "alpha_remap": classes, arena and copies of the align that is about to be planned (0 also when it fell back to the original bytes)
+int alphabet_scan(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint8_t sym[4]); // mwf_dbg.cpp: the class of mwf_alphabet_class and, class 1, the distinct bytes ascending (the last repeated up to four)
 double sketch_divergence(int32_t hit, int32_t tot, int32_t lt); // one pair's divergence from the hits of its query's `tot` 8-mers in a target of lt bases
 extern "C" int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value); // mwf_engine.cpp: forced kernels / geometries / failure paths for tests/ and profiles/
 // ---- mwf_async.cpp: submit / wait and the opt-in coalescing of single calls

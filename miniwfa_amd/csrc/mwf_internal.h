@@ -164,6 +164,23 @@ struct CigarOpsArgs {
 };
 int cigar_ops_block(int64_t max_len);                 // threads per pair for a batch whose longest pair has max_len bases of target + query
 int launch_cigar_ops(const CigarOpsArgs &a, int block, void *stream);
+// mwf_alphabet.hip: per-pair alphabet classes and the remapped copies of four-letter pairs ("alpha_remap"; one workgroup per pair; off the align path)
+struct AlphabetArgs {
+	const uint8_t *seqs;
+	const int64_t *t_off, *q_off;
+	const int32_t *tl, *ql;
+	const int32_t *ids;        // the pairs of the launch, one workgroup each (null: pairs 0 .. n_pairs)
+	int32_t n_pairs;
+	int32_t mode;              // 0: classify — cls[pair] and sym[pair] are written; 1: copy — the pairs with cls[pair] == 1 are written to the arena through sym[pair]
+	int8_t *cls;               // [pair] 0: every byte is one of A C G T; 1: at most four distinct bytes (and not class 0); 2: five or more
+	uint32_t *sym;             // [pair] class 1: the distinct bytes in ascending order, lowest byte first, the last one repeated up to four (byte b maps to "ACGT"[how many of the first three are below b]); else 0
+	// mode 1: where the copies of the launch's k-th pair go, as offsets from `seqs` (signed: the arena is an allocation of its own) — and the per-pair offset
+	// arrays the align kernels are given with `seqs`, which the workgroup enters them in (the host filled those with the batch's own offsets)
+	const int64_t *dst_t, *dst_q;
+	int64_t *out_t_off, *out_q_off;
+};
+int alphabet_block(int64_t max_len);                  // threads per pair for a batch whose longest pair has max_len bases of target + query
+int launch_alphabet(const AlphabetArgs &a, int block, void *stream);
 int  bigring_kernel_occupancy();                     // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
 int  batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ring16);   // resident workgroups per CU for that block size
 

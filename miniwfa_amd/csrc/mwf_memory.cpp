@@ -382,12 +382,18 @@ mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, con
 	b->seq_bytes = seq_bytes;
 	// the host touches every byte anyway: note which pairs the 2-bit sequence copy cannot hold, so that they never take the
 	// device round trip through ST_ALPHABET
-	b->h_acgt.resize((size_t)n);
+	// (... and of those pairs the alphabet class, mwf_alphabet_class: what "alpha_remap" needs to know at the batch's first align, when the caller's bytes are gone)
+	b->h_acgt.resize((size_t)n), b->h_alpha.assign((size_t)n, 0), b->h_sym.assign((size_t)n, 0);
 	auto classify = [&](int32_t i0, int32_t i1) {
 		for (int32_t i = i0; i < i1; ++i) {
 			const uint8_t *pt = ts ? (const uint8_t*)ts[i] : (const uint8_t*)packed + p_t_off[i];
 			const uint8_t *pq = ts ? (const uint8_t*)qs[i] : (const uint8_t*)packed + p_q_off[i];
 			b->h_acgt[i] = plain_acgt(pt, (size_t)tl[i]) && plain_acgt(pq, (size_t)ql[i]) ? 1 : 0;
+			if (!b->h_acgt[i]) {
+				uint8_t sym[4] = {0, 0, 0, 0};
+				b->h_alpha[i] = (int8_t)alphabet_scan(pt, (size_t)tl[i], pq, (size_t)ql[i], sym);
+				if (b->h_alpha[i] == 1) b->h_sym[i] = (uint32_t)sym[0] | (uint32_t)sym[1] << 8 | (uint32_t)sym[2] << 16 | (uint32_t)sym[3] << 24;
+			}
 		}
 	};
 	b->div_est = estimate_divergence(n, tl, ql, [&](int32_t i, bool target) -> const uint8_t* {
@@ -448,8 +454,126 @@ mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, con
 		mwf_gpu_batch_free(b);
 		return nullptr;
 	}
+	b->h_acgt_host = b->h_acgt;
 	lap("packed into the pinned buffer, copies enqueued, classification joined");
 	return b;
+}
+
+// ---- "alpha_remap": four-letter pairs on the 2-bit paths (kernels: mwf_alphabet.hip) --------------------------------------------------------
+
+// back to the batch's own bytes: the plan reads the upload's view of them again (wrapped batches: none)
+static void alpha_off(mwf_gpu_batch_t *b)
+{
+	if (b->alpha_active) b->h_acgt = b->h_acgt_host, b->plan.valid = false;
+	b->alpha_active = false;
+	b->d_rt_off = b->d_rq_off = nullptr;
+}
+
+// Called by mwf_gpu_batch_align before it plans.  With the tunable on: the classes of the batch's pairs (uploaded: known from the host twin; wrapped: one
+// classification launch over the current contents and one wait, every align), the arena with one copy of every class-1 pair — its bytes mapped onto
+// A/C/G/T, every sequence on a 16-byte boundary, 64 readable bytes in front of the first and behind the last — and per-pair offset arrays that address
+// those copies from the batch's own `seqs` base (the align kernels form seqs + int64 offset and nothing else, dev::pair_mem: no kernel changes).  The plan
+// then sees classes 0 and 1 as plain pairs and class 2 as known byte-wise ones; it is dropped whenever that view changed.
+// The copies are made once for an uploaded batch and at every align of a wrapped one (its contents may have changed: a stale copy would be a wrong answer).
+// An arena that does not fit what is free leaves the batch on its own bytes, as with the tunable off (the classes are still reported).
+int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
+{
+	g->alpha_timed[0] = g->alpha_timed[1] = false;
+	if (!g->alpha_remap) {
+		alpha_off(b);
+		b->alpha_known = false;
+		return 0;
+	}
+	const int32_t n = b->n;
+	const size_t N = (size_t)n;
+	for (hipEvent_t &e : g->ev_alpha)
+		if (!e) HIP_TRY(g, hipEventCreate(&e));
+	int64_t max_len = 0;
+	for (int32_t i = 0; i < n; ++i) max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+	const int block = alphabet_block(max_len);
+	if (ensure(g, b->alpha_cls, N * 5)) return -1;
+	AlphabetArgs a{};
+	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
+	a.sym = (uint32_t*)b->alpha_cls.p, a.cls = (int8_t*)(a.sym + N);
+	bool changed = !b->alpha_known;
+	if (!b->owns_inputs) {
+		a.n_pairs = n, a.mode = 0;
+		HIP_TRY(g, hipEventRecord(g->ev_alpha[0], g->stream));
+		if (launch_alphabet(a, block, g->stream)) { g->err = "kernel launch failed (alphabet classes)"; return -1; }
+		HIP_TRY(g, hipEventRecord(g->ev_alpha[1], g->stream));
+		g->alpha_timed[0] = true;
+		std::vector<char> back(N * 5);
+		if (download(g, back.data(), b->alpha_cls.p, N * 5)) return -1;
+		changed = changed || b->h_alpha.size() != N || memcmp(b->h_sym.data(), back.data(), N * 4) != 0 || memcmp(b->h_alpha.data(), back.data() + N * 4, N) != 0;
+		if (changed) {
+			b->h_sym.resize(N), b->h_alpha.resize(N);
+			memcpy(b->h_sym.data(), back.data(), N * 4), memcpy(b->h_alpha.data(), back.data() + N * 4, N);
+		}
+	} else if (!b->alpha_laid_out) {
+		if (upload_segments(g, (char*)b->alpha_cls.p, std::vector<Seg>{Seg{b->h_sym.data(), N * 4}, Seg{b->h_alpha.data(), N}})) return -1;
+	}
+	b->alpha_known = true;
+	const bool lay_out = !b->alpha_laid_out || (!b->owns_inputs && changed);
+	// the arena: [t_off: n int64 | q_off: n int64 | dst_t, dst_q: one int64 each per class-1 pair | their ids: int32 | 64 bytes | copies | 64 bytes]
+	const size_t hdr = align_up(N * 36, 16) + 64;
+	int64_t n1 = 0;
+	if (lay_out) {
+		std::vector<int64_t> dst(2 * N, 0);
+		std::vector<int32_t> ids(N, 0);
+		int64_t pos = 0;
+		for (int32_t i = 0; i < n; ++i) {
+			if (b->h_alpha[i] != 1) continue;
+			dst[(size_t)n1] = pos, pos += (int64_t)align_up((size_t)b->h_tl[i], 16);
+			dst[N + (size_t)n1] = pos, pos += (int64_t)align_up((size_t)b->h_ql[i], 16);
+			ids[(size_t)n1++] = i;
+		}
+		b->alpha_laid_out = false;
+		if (n1 > 0) {
+			const size_t need = hdr + (size_t)pos + 64;
+			bool fits = true;
+			if (g->alpha_arena_budget >= 0) fits = (int64_t)need <= g->alpha_arena_budget;
+			else if (b->alpha_arena.bytes < need) {
+				size_t fr = 0, tot = 0;
+				if (hipMemGetInfo(&fr, &tot) != hipSuccess) (void)hipGetLastError(), fr = 0;
+				fits = need <= fr / 5 * 4 + b->alpha_arena.bytes;
+			}
+			if (fits && ensure(g, b->alpha_arena, need)) g->err.clear(), fits = false;
+			if (!fits) { // as with the tunable off
+				alpha_off(b);
+				return 0;
+			}
+			char *base = (char*)b->alpha_arena.p;
+			// (offsets from the batch's `seqs`: a difference of two device addresses, negative when the arena lies below the batch)
+			const int64_t rel = (int64_t)((intptr_t)(base + hdr) - (intptr_t)b->d_seqs);
+			for (int64_t k = 0; k < n1; ++k) dst[(size_t)k] += rel, dst[N + (size_t)k] += rel;
+			if (upload_segments(g, base + N * 16, std::vector<Seg>{Seg{dst.data(), N * 16}, Seg{ids.data(), N * 4}})) return -1;
+		}
+		b->alpha_laid_out = true;
+	} else {
+		for (int32_t i = 0; i < n; ++i) n1 += b->h_alpha[i] == 1;
+	}
+	if (n1 > 0 && (lay_out || !b->owns_inputs)) {
+		char *base = (char*)b->alpha_arena.p;
+		a.out_t_off = (int64_t*)base, a.out_q_off = a.out_t_off + N;
+		a.dst_t = a.out_q_off + N, a.dst_q = a.dst_t + N, a.ids = (const int32_t*)(a.dst_q + N);
+		a.n_pairs = (int32_t)n1, a.mode = 1;
+		// every pair's own offsets first (a wrapped batch's live on the device only); the copy launch then enters the class-1 pairs'
+		HIP_TRY(g, hipMemcpyAsync(a.out_t_off, b->d_t_off, N * 8, hipMemcpyDeviceToDevice, g->stream));
+		HIP_TRY(g, hipMemcpyAsync(a.out_q_off, b->d_q_off, N * 8, hipMemcpyDeviceToDevice, g->stream));
+		HIP_TRY(g, hipEventRecord(g->ev_alpha[2], g->stream));
+		if (launch_alphabet(a, block, g->stream)) { g->err = "kernel launch failed (alphabet copy)"; return -1; }
+		HIP_TRY(g, hipEventRecord(g->ev_alpha[3], g->stream));
+		g->alpha_timed[1] = true;
+	}
+	b->d_rt_off = n1 > 0 ? (const int64_t*)b->alpha_arena.p : b->d_t_off;
+	b->d_rq_off = n1 > 0 ? (const int64_t*)b->alpha_arena.p + N : b->d_q_off;
+	if (!b->alpha_active || changed) {
+		b->h_acgt.resize(N);
+		for (int32_t i = 0; i < n; ++i) b->h_acgt[i] = b->h_alpha[i] != 2;
+		b->plan.valid = false;
+	}
+	b->alpha_active = true;
+	return 0;
 }
 
 } // namespace host

@@ -332,7 +332,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
-	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
+	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
 	a.order = d_order, a.n_pairs = n_items;
 	a.timeline = g->timeline;
 	// A launch of one workgroup per pair on the kernels that take it (lane, mid, packed band) needs no work counter: workgroup i aligns
@@ -567,7 +567,7 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	}
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
-	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
+	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
 	a.n_pairs = b->n;
 	a.pen = P;
 	a.want_cigar = cigar ? 1 : 0;
@@ -686,7 +686,8 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false; // (summaries and maps describe the previous align's CIGARs)
 	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
 	g->stats = mwf_gpu_stats_t{};
-	if (b->n == 0) { b->aligned = b->finalized = true; return 0; }
+	if (b->n == 0) { b->aligned = b->finalized = true, b->alpha_known = g->alpha_remap != 0; return 0; } // (an empty batch: nothing to classify or copy, and with "alpha_remap" 1 its zero classes are known)
+	if (alpha_prepare(g, b)) return -1; // ("alpha_remap": classes and copies first — the plan below follows them)
 	const bool cigar = (opt->flag & MWF_F_CIGAR) != 0;
 	{ // Where the result arrays lie.  A small score-only batch (the single pair of a drop-in call) gets them in a page of pinned host
 	  // memory that the kernels write directly: results() then waits for the stream and reads them — no copy to enqueue and wait
@@ -992,7 +993,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 				// the order array, which gets the final order below
 				if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{order.data() + lo, (size_t)(hi - lo) * 4}})) return -1;
 				b->h_order.clear();
-				if (launch_pair_sketch(b->d_seqs, b->d_t_off, b->d_tl, b->d_q_off, b->d_ql, b->d_order, hi - lo, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
+				if (launch_pair_sketch(b->d_seqs, b->alpha_active ? b->d_rt_off : b->d_t_off, b->d_tl, b->alpha_active ? b->d_rq_off : b->d_q_off, b->d_ql, b->d_order, hi - lo, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
 				std::vector<int32_t> hits((size_t)(hi - lo));
 				HIP_TRY(g, hipMemcpyAsync(hits.data(), b->d_dbg4, hits.size() * 4, hipMemcpyDeviceToHost, g->stream)); // (scratch behind the results: written by this align's kernels only with MWF_F_DEBUG)
 				HIP_TRY(g, hipStreamSynchronize(g->stream));
