@@ -58,6 +58,10 @@ constexpr bool kTabProbe = true;
 constexpr bool kTabProbe = false;
 #define MWF_BAND2_KERNEL wfa_band2_kernel
 #endif
+// The table form's chunk chain (band2_pass: kChain).  A slot keeps its chunk for hundreds of penalties, and what the probe derives from the chunk alone — the room
+// bounds rj of the lane's columns, the query's table index less j — is kept per slot in registers, computed where the slot's chunk is assigned (remap), for the
+// instantiations that hold it within their register budget: 512 x 3 with and without traceback, 512 x 4 score-only (512 x 4 with traceback stands at 127 VGPRs).
+constexpr bool band2_geo_cached(int T, int K, bool TB) { return kTabProbe && T == 512 && (K == 3 || (K == 4 && !TB)); }
 constexpr int kTabSlack = 258; // table entries beyond tl + ql: target position tl, query position -1, and the query positions a chunk's columns beyond cmax clamp to (up to ql + 255)
 
 __device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
@@ -329,6 +333,11 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	constexpr bool BI = is_span(T, K) || BI4; // biased offsets with range checks (wide_bias): the span geometry and the four-slot 512-thread one's copy for long pairs
 	constexpr bool TAB = kTabProbe && S2; // the first probe reads the 8-mer table in front of the 2-bit copies
 	constexpr int FULL = TAB ? 8 : S2 ? 16 : 8; // bases the first probe of the match extension looks at
+	constexpr bool kChain = TAB;                          // the table form: the rare tests of a chunk are marked as such, an interior chunk without a long run falls through
+	constexpr bool kGeo = TAB && band2_geo_cached(T, K, TB); // ... and the chunk's probe geometry is read from the slot's registers
+	// a test that is rarely true, for the forms that say so; a macro of this function alone (#undef behind it), written in the condition itself: the hint is lowered
+	// before inlining and does not survive a function or lambda boundary
+#define MWF_RARE(x) (kChain ? __builtin_expect((x), 0) != 0 : (x))
 	// FOLD (score-only, gap-open lag - mismatch lag == e1, i.e. o1 == x as in the default penalties): the row a penalty reads for its
 	// mismatch term, H[s-x], IS the row the first gap piece opens from e1 penalties later (miniwfa.c:267-278: both E1 and F1 take
 	// max(H[s-o1-e1], E1/F1[s-e1]) of a neighbouring column).  The registers that hold E1/F1 of the last e1 penalties therefore hold
@@ -437,6 +446,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 
 	// chunk of every slot of this wave under the mapping that starts at chunk gl (changes only when gl does)
 	int32_t gl = (wf_lo > 1 ? wf_lo - 1 : 1) >> 8, gk[K];
+	// (kGeo: the slot's probe geometry, a function of gk[k], the lane, tl and ql — the expressions of the chunk body, evaluated here.  gk[k] is assigned nowhere
+	// else, so the registers are never stale.)
+	int32_t grjA[K], grjB[K], gdA[K];
 	auto remap = [&](int32_t g_lo) {
 		const int32_t base = g_lo - g_lo % NWK;
 #pragma unroll
@@ -444,6 +456,11 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			int32_t g = base + wave + NW * k;
 			if (g < g_lo) g += NWK;
 			gk[k] = g;
+			if (kGeo) {
+				const int32_t cbp = both16(g * kChunk), xAc = pk_subsat(pk_subsat(T0, cbp), RA);
+				grjA[k] = pk_minu(xAc, TLp), grjB[k] = pk_minu(pk_subsat(xAc, 0x00010001), TLp);
+				gdA[k] = pk_add(pk_add(RA, cbp), 0x00010001);
+			}
 		}
 	};
 	remap(gl);
@@ -616,7 +633,10 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		if (kEpoch ? (st & (1u << 24)) != 0 : (ga >= 1 && wave == (ga - 1) % NW)) *(int2*)(rown + ((uint32_t)((ga - 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
 		if (kEpoch ? (st & (1u << 25)) != 0 : wave == (gb + 1) % NW) *(int2*)(rown + ((uint32_t)((gb + 1) << 9) + lane8)) = make_int2(kDeadPair, kDeadPair);
 #if MWF_B2_TIMING == 2
-		bool chunk_timed = false;
+#ifndef MWF_B2_TIMED_CHUNK
+#define MWF_B2_TIMED_CHUNK 0 // which of the wave's running chunks of a penalty is timed: 0 the first, 1 the second (zeros where the wave runs fewer)
+#endif
+		int chunks_seen = 0;
 		uint32_t ct[4] = {0, 0, 0, 0};
 #endif
 #pragma unroll
@@ -638,7 +658,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- rows: H at the three lags (one 8-byte load each) and the word next to the chunk for the two gap-open rows
 #if MWF_B2_TIMING == 2
 			uint64_t tc0 = 0, tc1 = 0, tc2 = 0, tc3 = 0, tc4 = 0;
-			const bool timed = !chunk_timed;
+			const bool timed = chunks_seen++ == MWF_B2_TIMED_CHUNK;
 			if (timed) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc0) :: "memory");
 #endif
 			const uint32_t off = (uint32_t)(cb << 1) + lane8;
@@ -665,8 +685,17 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			const int32_t pf1B = FOLD ? g1pB : pk_max(o1pB, g1pB), pf2B = pk_max(o2pB, g2pB);
 			int32_t nf1A = pk_add(pf1A, ONE), nf2A = pk_add(pf2A, ONE), nf1B = pk_add(pf1B, ONE), nf2B = pk_add(pf2B, ONE);
 			const int32_t mA = pk_add(HX.x, ONE), mB = pk_add(HX.y, ONE);
-			int32_t hA = pk_max(pk_max(mA, pk_max(ne1A, ne2A)), pk_max(nf1A, nf2A));
-			int32_t hB = pk_max(pk_max(mB, pk_max(ne1B, ne2B)), pk_max(nf1B, nf2B));
+			// (kChain: the four partial maxima first, then the two last ones — one VALU instruction between the halves' last maxima, so that neither follows the
+			// packed instruction it depends on directly: the hazard nop between A's last two maxima is gone; checked in the assembly, 4 -> 3 s_nop per chunk)
+			int32_t hA, hB;
+			if (kChain) {
+				const int32_t gA = pk_max(mA, pk_max(ne1A, ne2A)), gB = pk_max(mB, pk_max(ne1B, ne2B)), fA = pk_max(nf1A, nf2A), fB = pk_max(nf1B, nf2B);
+				__builtin_amdgcn_sched_group_barrier(0x2, 1, 0);
+				hA = pk_max(gA, fA), hB = pk_max(gB, fB);
+			} else {
+				hA = pk_max(pk_max(mA, pk_max(ne1A, ne2A)), pk_max(nf1A, nf2A));
+				hB = pk_max(pk_max(mB, pk_max(ne1B, ne2B)), pk_max(nf1B, nf2B));
+			}
 #if MWF_B2_TIMING == 2
 			if (timed) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc1) : "v"(hA), "v"(hB) : "memory");
 #endif
@@ -695,9 +724,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// Both subtractions saturate: a running chunk has cb <= cmax today — hi <= cmax, an ageing slot was in the window once, the remap waits for it to
 			// age out — but the probe's bounds must not rest on that: a chunk beyond cmax gets rj = 0 like a column beyond it, not a wrapped difference)
 			const int32_t xAc = TAB ? pk_subsat(pk_subsat(T0, cbp), RA) : xA;
-			const int32_t rjA = pk_minu(xAc, TLp), rjB = pk_minu(TAB ? pk_subsat(xAc, ONE) : pk_sub(xA, ONE), TLp);
+			const int32_t rjA = kGeo ? grjA[k] : pk_minu(xAc, TLp), rjB = kGeo ? grjB[k] : pk_minu(TAB ? pk_subsat(xAc, ONE) : pk_sub(xA, ONE), TLp);
 			// (the table form: the query's table index is j + c + 1, no target length in it)
-			const int32_t dA = TAB ? pk_add(pk_add(RA, cbp), ONE) : pk_sub(pk_add(RA, cbp), TL1), dB = pk_add(dA, ONE);
+			const int32_t dA = kGeo ? gdA[k] : TAB ? pk_add(pk_add(RA, cbp), ONE) : pk_sub(pk_add(RA, cbp), TL1), dB = pk_add(dA, ONE);
 			// ---- the rare work in front of the extension — the chunk sticks out of the window, holds a window edge, a shrink is near — behind ONE
 			// uniform test: an interior chunk (most chunks) pays one branch for the three (a uniform branch costs a wave 17-31 cycles,
 			// profiles/r05/branch_rates_microbench.txt): 1024 x 10 kb -2 % score-only, -3 % with CIGAR.  (The rare work behind the extension — end
@@ -709,8 +738,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- a chunk that sticks out of the window: the columns outside are not computed by the reference — dead
 			int32_t outA = 0, outB = 0; // 0xffff in the halves of columns outside [lo, hi]
 			uint32_t bits = 0, gbits = 0;
-			if (special) { // uniform
-			if (!inside) { // uniform
+			if (MWF_RARE(special)) { // uniform
+			if (MWF_RARE(!inside)) { // uniform
 				const int32_t lo_r = both16(min(max(lo - cb, 0), 256)), hi_r1 = both16(min(max(hi - cb + 1, 0), 256));
 				const int32_t RB = pk_add(RA, 0x00010001), RB1 = pk_add(RA, 0x00020002);
 				outA = pk_nonzero_mask(pk_subsat(lo_r, RA) | pk_subsat(RB, hi_r1));
@@ -860,7 +889,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			const int32_t pendp = pk_subsat(m9A, FULLp) | pk_subsat(m9B, FULLp);
 			// ---- a run of >= FULL matches continues (the cells near the alignment path, and one first probe in 4^FULL by chance).  Each
 			// lane first walks its own runs, four trips at most; what is still open then the whole wave walks.
-			if (__ballot(pendp != 0)) {
+			if (MWF_RARE(__ballot(pendp != 0) != 0)) {
 				const int32_t tb0 = TAB ? fresh(A).band_lds_tab : 0; // where the target's 2-bit copy starts
 				int32_t hv[4] = {half_of(hA, 0) + B, half_of(hB, 0) + B, half_of(hA, 1) + B, half_of(hB, 1) + B}; // true offsets
 				int32_t nmat[4] = {(int32_t)((uint32_t)nmA & 0xffffu), (int32_t)((uint32_t)nmB & 0xffffu), (int32_t)((uint32_t)nmA >> 16), (int32_t)((uint32_t)nmB >> 16)};
@@ -908,7 +937,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- termination test of the extension sweep (miniwfa.c:405-409): only column ql+1 can hold the end cell
 			unsigned long long fm = 0;
 			int32_t done_info = 0;
-			if ((uint32_t)(cfin - cb) < (uint32_t)kChunk && cfin >= lo && cfin <= hi) { // uniform
+			if (MWF_RARE((uint32_t)(cfin - cb) < (uint32_t)kChunk && cfin >= lo && cfin <= hi)) { // uniform
 				const int32_t rel = cfin - cb, hi_half = (rel >> 1) & 1;
 				const int32_t hv = half_of((rel & 1) ? hxB : hxA, hi_half) + B, nm = (int32_t)((uint32_t)((rel & 1) ? nmB : nmA) >> (hi_half ? 16 : 0) & 0xffffu);
 				const uint32_t f = (uint32_t)(lane == (rel >> 2)) & (uint32_t)(hv == tl - 1) & inm_bit(ql - tl, hv - nm, tl, ql);
@@ -920,13 +949,12 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 #if MWF_B2_TIMING == 2
 			if (timed) {
 				asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc4) : "v"(hxA), "v"(hxB) : "memory");
-				chunk_timed = true;
 				ct[0] = (uint32_t)min(tc1 - tc0, (uint64_t)4095), ct[1] = (uint32_t)min(tc2 - tc1, (uint64_t)4095);
 				ct[2] = (uint32_t)min(tc3 - tc2, (uint64_t)4095), ct[3] = (uint32_t)min(tc4 - tc3, (uint64_t)4095);
 			}
 #endif
 			if (TB && c0 >= origin && c0 <= hi) *(uint32_t*)(M.tb + tb_used - origin + c0) = tbw;
-			if (track_good) {
+			if (MWF_RARE(track_good)) {
 				unsigned long long *gword = M.good + (int64_t)newH * fresh(A).GW + g * 4;
 #pragma unroll
 				for (int i = 0; i < 4; ++i) {
@@ -935,7 +963,10 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 				}
 			}
 			if (fm) bits |= 4u | (uint32_t)__builtin_amdgcn_readlane(done_info, (int32_t)__builtin_ctzll(fm)) << 4;
-			if (bits && lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
+			if (kChain) { // (bits is uniform: a scalar test that falls through instead of an exec mask and a taken branch)
+				if (MWF_RARE(bits != 0))
+					if (lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
+			} else if (bits && lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
 		}
 
 		if (forecast) {
@@ -1042,6 +1073,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	R.s = s, R.cells = est_window ? -(int64_t)est_window : cells; // (a pair handed back early: the window it is expected to need, negated, for the host's choice of the next kernel)
 	return R;
 }
+#undef MWF_RARE
 
 // Workgroups share a CU: 2 x 512, 4 x 256, 8 x 128 or 16 x 64 threads = 4 waves per SIMD, i.e. at most 128 VGPRs; with traceback
 // the smaller ones get 168 (3 per SIMD).  768 threads: one workgroup per CU.
