@@ -62,7 +62,8 @@ void mwf_opt_init(mwf_opt_t *opt);
  * are 32-bit).  x, e1, e2 >= 1 and o1, o2 >= 0, as the reference requires implicitly (miniwfa.c:390-392).
  * The fast paths hold sequences at 2 bits per base, which takes pairs of plain upper-case A/C/G/T; with "alpha_remap" (below, or MWF_ALPHA_REMAP=1 for
  * the calls that create their engines themselves) also any pair with at most four distinct bytes — lower case, U for T, bases coded 0..3.  A pair with
- * five or more distinct bytes (an N, mixed case) still runs on the byte-wise copies: one geometry of the band kernel, else the generic kernel.
+ * five or more distinct bytes (an N, mixed case) still runs on the byte-wise copies: one geometry of the band kernel, else the generic kernel — unless "alpha16"
+ * (below, or MWF_ALPHA16=1) is set as well: under gap extensions (2,1) a pair of 5 to 16 distinct bytes then takes the band kernel's 4-bit copies (mwf_band2_nib.hip).
  * Every penalty set gives the reference's answer; which kernels serve it depends on the gap extensions (e1, e2): the whole-device kernel for
  * long pairs ("coop_min_len" below) takes (2,1), (2,2), (1,1) and e1 in {3, 4} with e2 in {1, 2} (minimap2's asm5 / asm20-like sets); under any
  * other pair of extensions long pairs run on the generic one-workgroup-per-pair kernel (about ten times slower on a 150 kb pair).  The packed
@@ -236,7 +237,14 @@ int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int
  * 0 and 2 all 256 entries are 0.  Needs no device.  Never reads outside ts[0,tl) / qs[0,ql). */
 int32_t mwf_alphabet_class(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256]);
 
-/* Per-pair class (0, 1, 2 as above) of the batch's last align under "alpha_remap" 1, copied to host_out[n].  Fails (negative; mwf_gpu_last_error)
+/* The same with one class more, as the engine sees a pair under "alpha16" 1: 0 and 1 as above, 3 five to sixteen distinct bytes, 2 seventeen or more.  A class-3
+ * pair can be aligned as its image under the bijection that gives the distinct bytes, in ascending byte value, the codes 0 ... 15: the image byte is
+ * MWF_ALPHA16_TAG | code.  map: for class 1 as mwf_alphabet_class gives it; for class 3 the image byte of every byte that occurs, 0 elsewhere; all zero for
+ * classes 0 and 2.  Needs no device.  Never reads outside ts[0,tl) / qs[0,ql). */
+#define MWF_ALPHA16_TAG 0x40 /* the fixed high nibble of a class-3 image byte */
+int32_t mwf_alphabet_class16(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256]);
+
+/* Per-pair class (0, 1, 2 as above; with "alpha16" 1: 0, 1, 2, 3 as mwf_alphabet_class16) of the batch's last align under "alpha_remap" 1, copied to host_out[n].  Fails (negative; mwf_gpu_last_error)
  * before the first align and when that align ran with the tunable off. */
 int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out);
 
@@ -260,7 +268,7 @@ void mwf_gpu_get_stats(const mwf_gpu_t *g, mwf_gpu_stats_t *st);
  * wavefront slice the core pass opened for `pair`; returns the number of penalties written (<= cap). */
 int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, int32_t pair, int32_t *lohi, int32_t cap);
 
-/* Tunables (call before align; every call invalidates the cached plans of the engine's batches).  Fifteen names and one action:
+/* Tunables (call before align; every call invalidates the cached plans of the engine's batches).  Sixteen names and one action:
  *   "tb_budget_mb"      traceback arena of the one-workgroup-per-pair kernels (0 = automatic: four fifths of what is free, at most a quarter of the device)
  *   "lowmem_budget_mb"  whole-device kernel, opt.step > 0: a first-pass traceback above this many MB switches to the two-pass form whose first pass stores none (0 = a quarter of the device)
  *   "coop_min_len"      tl + ql from which a batch of at most sixteen pairs runs on the whole-device kernel (0 = 20 000 score-only, 15 000 with CIGAR);
@@ -286,6 +294,14 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
  *                       variable is read once per process and applied to an engine when a call creates it, so it must be set before the first such call.  The batch's divergence estimate
  *                       ("div_aware") is still taken from the original bytes through (byte >> 1) & 3: lower case and U read as their upper-case letters, but codings that collapse under
  *                       it (bytes 0..3 read as 0, 0, 1, 1) can get other size classes, and so other re-run counts, than the plain twin — never other answers.
+ *   "alpha16"           0 (default) or 1; acts only together with "alpha_remap" 1 (with "alpha_remap" 0: no buffer, no launch).  1: a pair of 5 to 16 distinct bytes (mwf_alphabet_class16
+ *                       class 3: an N, IUPAC codes, soft-masked mixed case) is copied into the same arena with its bytes mapped to MWF_ALPHA16_TAG | code, whatever the penalties; every
+ *                       kernel compares those image bytes as it would the originals — same s, n_iter and CIGAR.  Under gap extensions (2,1), with "seq2bit" / "band_pack" /
+ *                       "band_span" not switched off, such a pair takes the packed band kernel's 4-bit form (mwf_band2_nib.hip: 512 threads x 3 or 4 chunk slots wherever a plain pair
+ *                       would take a 64 ... 512-thread geometry, the span geometry where it would take the biased 512-thread copies or the span geometry) instead of the byte-wise
+ *                       768-thread geometry or the generic kernel; the lane, mid, whole-device and generic routes and every other penalty set are as without it.  Pairs of 17 or more
+ *                       distinct bytes (class 2) stay byte-wise.  MWF_ALPHA16=1 (read once per process) applies "alpha_remap" 1 and "alpha16" 1 to the engines the drop-in calls
+ *                       create.  Not for batches of reads: those take the lane kernel's byte-wise copy either way and only pay for the copies.
  *   "trim"              (action) free the engine's workspace pools; they grow back on demand.
  * (The hooks tests and profiling scripts force kernels, geometries and failure paths with — "force_kind", "block", "sys_c" ... — are a separate, undeclared entry point,
  * mwf_gpu_test_hook in csrc/mwf_engine.cpp.) */

@@ -76,7 +76,7 @@ ABI_SYMBOLS = (
     "mwf_gpu_debug_band",
     "mwf_cigar_summary", "mwf_gpu_batch_dev_cigars", "mwf_gpu_batch_summarize", "mwf_gpu_batch_dev_summary", "mwf_gpu_batch_summary",
     "mwf_gpu_batch_map", "mwf_gpu_batch_dev_map", "mwf_gpu_batch_map_fetch",
-    "mwf_alphabet_class", "mwf_gpu_batch_alphabet",
+    "mwf_alphabet_class", "mwf_alphabet_class16", "mwf_gpu_batch_alphabet",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -174,6 +174,8 @@ def lib() -> C.CDLL:
     L.mwf_gpu_batch_map_fetch.restype = C.c_int
     L.mwf_alphabet_class.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p]
     L.mwf_alphabet_class.restype = C.c_int32
+    L.mwf_alphabet_class16.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p]
+    L.mwf_alphabet_class16.restype = C.c_int32
     L.mwf_gpu_batch_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mwf_gpu_batch_alphabet.restype = C.c_int
     L.mwf_gpu_test_alpha_ms.argtypes = [C.c_void_p, P(C.c_double)]
@@ -342,6 +344,18 @@ def alphabet_class(t: bytes, q: bytes):
     return int(cls), bytes(m)
 
 
+ALPHA16_TAG = 0x40  # MWF_ALPHA16_TAG: the high nibble of a class-3 image byte
+
+
+def alphabet_class16(t: bytes, q: bytes):
+    """mwf_alphabet_class16 -> (class, map): the classes an engine reports under "alpha16" 1 — 0 and 1 as alphabet_class, 3 five to sixteen distinct
+    bytes, 2 seventeen or more.  map: for class 1 as alphabet_class gives it; for class 3 ALPHA16_TAG | code (codes 0 ... 15 by ascending byte value)
+    for every byte that occurs and 0 elsewhere; else all 0 — bytes(t).translate(map) is the pair as "alpha16" aligns it.  Needs no device."""
+    m = (C.c_uint8 * 256)()
+    cls = lib().mwf_alphabet_class16(len(t), t, len(q), q, m)
+    return int(cls), bytes(m)
+
+
 class Engine:
     """mwf_gpu_t: one device, one stream, one workspace pool."""
 
@@ -459,7 +473,7 @@ class Batch:
         return out[:rc]
 
     def alphabet(self) -> np.ndarray:
-        """Per-pair alphabet class (int8: 0, 1, 2 as alphabet_class) of the last align under "alpha_remap" 1; raises before the first align and
+        """Per-pair alphabet class (int8: 0, 1, 2 as alphabet_class; with "alpha16" 1: 0, 1, 2, 3 as alphabet_class16) of the last align under "alpha_remap" 1; raises before the first align and
         when that align ran with the tunable off (mwf_gpu_batch_alphabet)."""
         out = np.zeros(max(1, self.n), dtype=np.int8)
         rc = lib().mwf_gpu_batch_alphabet(self.eng.h, self.h, out.ctypes.data)

@@ -1,4 +1,4 @@
-// mwf_alphabet.hip — per-pair alphabet classes and the remapped copies of four-letter pairs, on the device (gfx950, wave64).  Off the align
+// mwf_alphabet.hip — per-pair alphabet classes and the remapped copies of pairs of at most four ("alpha_remap") or sixteen ("alpha16") distinct bytes, on the device (gfx950, wave64).  Off the align
 // path: nothing here runs unless the engine's "alpha_remap" tunable is 1 (alpha_prepare, mwf_memory.cpp).
 //
 // Every fast path holds sequences at 2 bits per base, which takes plain upper-case A/C/G/T.  The recurrence only needs the equality relation
@@ -9,10 +9,12 @@
 // One workgroup per pair, over an index list, two launches (AlphabetArgs::mode), no global atomics, plain vector stores:
 //   0  classify: the presence set of the pair's bytes — 256 bits, eight words per thread, gathered with 16-byte loads between a bytewise head
 //      (up to the first 16-byte boundary: the head of a sequence is not aligned) and a bytewise tail; OR-reduced across the wave in registers
-//      and across the waves through LDS.  Its population count and one mask give the class; thread 0 writes the class and, for class 1, the
-//      distinct bytes in ascending order.  A batch built from host memory skips this launch: the host twin saw the bytes while it packed.
-//   1  copy, class-1 pairs only: every byte b becomes "ACGT"[how many of the pair's three lowest distinct bytes are below b], 16 bytes per
+//      and across the waves through LDS.  Its population count and one mask give the class; thread 0 writes the class and, for classes 1 and 3, the
+//      distinct bytes in ascending order (sixteen bytes per pair).  A batch built from host memory skips this launch: the host twin saw the bytes while it packed.
+//   1  copy, class-1 pairs: every byte b becomes "ACGT"[how many of the pair's three lowest distinct bytes are below b], 16 bytes per
 //      thread and step (an unaligned load, an aligned store: the host puts every copy on a 16-byte boundary), head and tail bytewise.
+//      Class-3 pairs ("alpha16": five to sixteen distinct bytes, in ascending order the codes 0 ... 15): the workgroup first builds a 256-entry byte
+//      table in LDS — entry b = 0x40 | how many of the pair's symbols are below b — and the same copy loop looks every byte up in it.
 // The workgroup also enters the copies' offsets in the per-pair offset arrays the align kernels will be given.
 // No access leaves [t_off, t_off + tl) / [q_off, q_off + ql) of the source or [dst_t, dst_t + tl) / [dst_q, dst_q + ql) of the arena.
 // Geometry: the host picks the workgroup size for the launch from the longest pair of the batch (alphabet_block below), as mwf_cigar_ops.hip does.
@@ -63,6 +65,30 @@ __device__ __forceinline__ uint32_t remap4(uint32_t v, uint32_t m0, uint32_t m1,
 	return remap1(v & 0xffu, m0, m1, m2) | remap1((v >> 8) & 0xffu, m0, m1, m2) << 8 | remap1((v >> 16) & 0xffu, m0, m1, m2) << 16 | remap1(v >> 24, m0, m1, m2) << 24;
 }
 
+// class 3: through the workgroup's table (the caller's barrier stands between its stores and these reads)
+__device__ __forceinline__ uint32_t table4(const uint8_t *tab, uint32_t v)
+{
+	return (uint32_t)tab[v & 0xffu] | (uint32_t)tab[(v >> 8) & 0xffu] << 8 | (uint32_t)tab[(v >> 16) & 0xffu] << 16 | (uint32_t)tab[v >> 24] << 24;
+}
+
+template <int B>
+__device__ __forceinline__ void copy_range16(const uint8_t *src, uint8_t *dst, int32_t len, const uint8_t *tab)
+{
+	const int tid = (int)threadIdx.x;
+	const int32_t head = min(len, (int32_t)((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u)); // (0 where the host laid the arena out)
+	for (int32_t j = tid; j < head; j += B) dst[j] = tab[src[j]];
+	const int32_t n16 = (len - head) >> 4;
+	uint4 *w = (uint4*)(dst + head);
+	for (int32_t k = tid; k < n16; k += B) {
+		uint32_t q[4];
+		__builtin_memcpy(q, src + head + ((int64_t)k << 4), 16);
+		uint4 o;
+		o.x = table4(tab, q[0]), o.y = table4(tab, q[1]), o.z = table4(tab, q[2]), o.w = table4(tab, q[3]);
+		w[k] = o;
+	}
+	for (int32_t j = head + (n16 << 4) + tid; j < len; j += B) dst[j] = tab[src[j]];
+}
+
 template <int B>
 __device__ __forceinline__ void copy_range(const uint8_t *src, uint8_t *dst, int32_t len, uint32_t m0, uint32_t m1, uint32_t m2)
 {
@@ -91,12 +117,30 @@ __global__ __launch_bounds__(B) void alphabet_kernel(AlphabetArgs A)
 	const int32_t tl = A.tl[pair], ql = A.ql[pair];
 	const uint8_t *t = A.seqs + A.t_off[pair], *q = A.seqs + A.q_off[pair];
 	if (MODE == 1) {
-		if (A.cls[pair] != 1) return;
-		const uint32_t s = A.sym[pair], m0 = s & 0xffu, m1 = (s >> 8) & 0xffu, m2 = (s >> 16) & 0xffu;
+		const int cls = A.cls[pair]; // (uniform: one pair per workgroup)
+		if (cls != 1 && cls != 3) return;
+		const uint32_t *sw = A.sym + (int64_t)pair * kAlphaSymWords;
 		uint8_t *base = const_cast<uint8_t*>(A.seqs);
 		const int64_t dt = A.dst_t[blockIdx.x], dq = A.dst_q[blockIdx.x];
-		copy_range<B>(t, base + dt, tl, m0, m1, m2);
-		copy_range<B>(q, base + dq, ql, m0, m1, m2);
+		if (cls == 3) {
+			__shared__ uint8_t s_tab[256];
+			uint32_t s4[kAlphaSymWords];
+#pragma unroll
+			for (int k = 0; k < kAlphaSymWords; ++k) s4[k] = sw[k];
+			for (int bb = tid; bb < 256; bb += B) { // (the symbols ascend and the last one is repeated: the count of those below b is b's code)
+				uint32_t rank = 0;
+#pragma unroll
+				for (int k = 0; k < 4 * kAlphaSymWords; ++k) rank += ((s4[k >> 2] >> (8 * (k & 3))) & 0xffu) < (uint32_t)bb ? 1u : 0u;
+				s_tab[bb] = (uint8_t)(0x40u | (rank & 15u));
+			}
+			__syncthreads();
+			copy_range16<B>(t, base + dt, tl, s_tab);
+			copy_range16<B>(q, base + dq, ql, s_tab);
+		} else {
+			const uint32_t s = sw[0], m0 = s & 0xffu, m1 = (s >> 8) & 0xffu, m2 = (s >> 16) & 0xffu;
+			copy_range<B>(t, base + dt, tl, m0, m1, m2);
+			copy_range<B>(q, base + dq, ql, m0, m1, m2);
+		}
 		if (tid == 0) A.out_t_off[pair] = dt, A.out_q_off[pair] = dq;
 		return;
 	}
@@ -127,9 +171,14 @@ __global__ __launch_bounds__(B) void alphabet_kernel(AlphabetArgs A)
 	uint32_t other = 0;
 #pragma unroll
 	for (int k = 0; k < 8; ++k) count += __popc(m[k]), other |= k == 2 ? (m[k] & ~kAcgtWord2) : m[k];
-	const int cls = other == 0 ? 0 : count <= 4 ? 1 : 2;
-	uint32_t sym = 0;
-	if (cls == 1) {
+	const int cls = other == 0 ? 0 : count <= 4 ? 1 : (A.alpha16 && count <= 16) ? 3 : 2;
+	uint32_t sym[kAlphaSymWords] = {0, 0, 0, 0};
+	auto put = [&](int at, uint32_t b) { // (constant indices once unrolled: the record stays in registers)
+#pragma unroll
+		for (int k = 0; k < kAlphaSymWords; ++k) sym[k] |= (at >> 2) == k ? b << (8 * (at & 3)) : 0u;
+	};
+	if (cls == 1 || cls == 3) {
+		const int fill = cls == 1 ? 4 : 16;
 		int have = 0;
 		uint32_t last = 0;
 #pragma unroll
@@ -137,14 +186,15 @@ __global__ __launch_bounds__(B) void alphabet_kernel(AlphabetArgs A)
 			uint32_t w = m[k];
 			while (w) {
 				last = (uint32_t)(32 * k + __ffs((int)w) - 1);
-				sym |= last << (8 * have++);
+				put(have++, last);
 				w &= w - 1;
 			}
 		}
-		for (; have < 4; ++have) sym |= last << (8 * have);
+		for (; have < fill; ++have) put(have, last);
 	}
 	A.cls[pair] = (int8_t)cls;
-	A.sym[pair] = sym;
+#pragma unroll
+	for (int k = 0; k < kAlphaSymWords; ++k) A.sym[(int64_t)pair * kAlphaSymWords + k] = sym[k];
 }
 
 template <int B>

@@ -54,10 +54,24 @@ constexpr int32_t kDeadPair = (int32_t)0x80008000u;
 #ifdef MWF_BAND2_TAB
 constexpr bool kTabProbe = true;
 #define MWF_BAND2_KERNEL wfa_band2_tab_kernel
+#elif defined(MWF_BAND2_NIB)
+constexpr bool kTabProbe = false;
+#define MWF_BAND2_KERNEL wfa_band2_nib_kernel
 #else
 constexpr bool kTabProbe = false;
 #define MWF_BAND2_KERNEL wfa_band2_kernel
 #endif
+// The 4-bit form (mwf_band2_nib.hip includes this file with MWF_BAND2_NIB set): the S2 paths — sequence copy, first probe, match walks — hold FOUR bits per base,
+// eight bases per dword, base j at bits 4*(j & 7) of dword j >> 3, packed from the image bytes of a pair of 5 to 16 distinct bytes ("alpha16": 0x40 | code,
+// mwf_alphabet.hip).  Everything that differs follows from two constants: kSeqSh, log2 of the bits per base, and kSeqDw, log2 of the bases per dword.  The kernel
+// carries a name of its own; with the macro unset both constants are the 2-bit form's and every expression folds to what it was.
+#ifdef MWF_BAND2_NIB
+constexpr bool kNib = true;
+#else
+constexpr bool kNib = false;
+#endif
+constexpr int kSeqSh = kNib ? 2 : 1, kSeqDw = kNib ? 3 : 4, kSeqPer = 1 << kSeqDw;
+constexpr uint32_t kNibTag = 0x40; // high nibble of an image byte (MWF_ALPHA16_TAG, include/miniwfa.h)
 // The table form's chunk chain (band2_pass: kChain).  A slot keeps its chunk for hundreds of penalties, and what the probe derives from the chunk alone — the room
 // bounds rj of the lane's columns, the query's table index less j — is kept per slot in registers, computed where the slot's chunk is assigned (remap), for the
 // instantiations that hold it within their register budget: 512 x 3 with and without traceback, 512 x 4 score-only (512 x 4 with traceback stands at 127 VGPRs).
@@ -134,15 +148,15 @@ __device__ __forceinline__ int32_t probe8_count(const Probe8 &p, int32_t j, int3
 // profiles/r02/lds_issue_rates_microbench.txt) and a run must be twice as long before the per-lane loop is entered.
 __device__ __forceinline__ uint32_t seq16(int32_t base, int32_t j)
 {
-	const uint32_t *p = (const uint32_t*)(lds2 + base + ((j >> 4) << 2));
-	return __builtin_amdgcn_alignbit(p[1], p[0], (uint32_t)j << 1);
+	const uint32_t *p = (const uint32_t*)(lds2 + base + ((j >> kSeqDw) << 2));
+	return __builtin_amdgcn_alignbit(p[1], p[0], (uint32_t)j << kSeqSh);
 }
 // leading equal bases of a 16-base probe result (0 bits = equal); huge for "no difference"
 __device__ __forceinline__ int32_t lead_eq2(uint32_t x)
 {
 	int32_t fb;
 	asm("v_ffbl_b32 %0, %1" : "=v"(fb) : "v"(x));
-	return (int32_t)((uint32_t)fb >> 1);
+	return (int32_t)((uint32_t)fb >> kSeqSh);
 }
 struct Probe16 { uint32_t t0, t1, q0, q1; };
 __device__ __forceinline__ void probe16_issue(Probe16 &p, int32_t qbase, int32_t j, int32_t iq)
@@ -156,19 +170,19 @@ __device__ __forceinline__ int32_t probe16_count(const Probe16 &p, int32_t j, in
 	return min(lead_eq2(__builtin_amdgcn_alignbit(p.t1, p.t0, (uint32_t)j << 1) ^ __builtin_amdgcn_alignbit(p.q1, p.q0, (uint32_t)iq << 1)), 17);
 }
 // exact-match run t[j..] == q[iq..] on the 2-bit copies, at most `room`, the first n0 known equal, walked by all 64 lanes:
-// 1024 bases per trip.  Arguments wave-uniform.
+// 1024 bases per trip (the 4-bit form: 8 bases per lane, 512 per trip).  Arguments wave-uniform.
 __device__ __forceinline__ int32_t run_wave16(int32_t qbase, int32_t j, int32_t iq, int32_t room, int32_t n0, int32_t tbase = 0)
 {
 	const int32_t lane = threadIdx.x & 63;
 	int32_t n = n0;
 	while (n < room) {
-		const int32_t off = n + 16 * lane;
+		const int32_t off = n + kSeqPer * lane;
 		int32_t m = 0;
-		if (off < room) m = min(min(lead_eq2(seq16(tbase, j + off) ^ seq16(qbase, iq + off)), 16), room - off);
-		const unsigned long long stop = __ballot(m < 16);
-		if (stop == 0) { n += 1024; continue; }
+		if (off < room) m = min(min(lead_eq2(seq16(tbase, j + off) ^ seq16(qbase, iq + off)), kSeqPer), room - off);
+		const unsigned long long stop = __ballot(m < kSeqPer);
+		if (stop == 0) { n += 64 * kSeqPer; continue; }
 		const int32_t first = (int32_t)__builtin_ctzll(stop);
-		n += 16 * first + __builtin_amdgcn_readlane(m, first);
+		n += kSeqPer * first + __builtin_amdgcn_readlane(m, first);
 		break;
 	}
 	return min(n, room);
@@ -204,6 +218,42 @@ __device__ __forceinline__ uint32_t pack2bit(const uint8_t *src, int32_t len, in
 			}
 		}
 		*(uint32_t*)(lds2 + base + 4 * w) = out;
+	}
+	return bad;
+}
+
+// The 4-bit form: image bytes (kNibTag | code) -> 4 bits per base into LDS at `base`, sixteen bytes (two dwords of the copy) per thread and step, two dwords of
+// slack behind the last base.  Returns nonzero when a byte does not carry the tag: the pair was not copied for this form (the host re-runs it byte-wise).
+template <int T>
+__device__ __forceinline__ uint32_t pack4bit(const uint8_t *src, int32_t len, int32_t base)
+{
+	uint32_t bad = 0;
+	const int32_t n_dw = (len >> 3) + 2;
+	for (int32_t w = 2 * (int32_t)threadIdx.x; w < n_dw; w += 2 * T) {
+		uint32_t out[2] = {0, 0};
+		const int32_t b0 = w << 3;
+		if (b0 + 16 <= len) {
+			uint32_t q[4];
+			__builtin_memcpy(q, src + b0, 16);
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				const uint32_t x = q[k];
+				bad |= (x & 0xf0f0f0f0u) ^ (kNibTag * 0x01010101u);
+				uint32_t c = x & 0x0f0f0f0fu;
+				c = (c | c >> 4) & 0x00ff00ffu;
+				c = (c | c >> 8) & 0xffffu;
+				out[k >> 1] |= c << (16 * (k & 1));
+			}
+		} else {
+#pragma unroll 1
+			for (int32_t k = 0; k < 16 && b0 + k < len; ++k) {
+				const uint32_t x = src[b0 + k];
+				bad |= (x & 0xf0u) ^ kNibTag;
+				out[k >> 3] |= (x & 0xfu) << (4 * (k & 7));
+			}
+		}
+		*(uint32_t*)(lds2 + base + 4 * w) = out[0];
+		if (w + 1 < n_dw) *(uint32_t*)(lds2 + base + 4 * w + 4) = out[1];
 	}
 	return bad;
 }
@@ -332,7 +382,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	constexpr int NW = T / 64, NWK = NW * K, D = (E1 > E2 ? E1 : E2) + 1;
 	constexpr bool BI = is_span(T, K) || BI4; // biased offsets with range checks (wide_bias): the span geometry and the four-slot 512-thread one's copy for long pairs
 	constexpr bool TAB = kTabProbe && S2; // the first probe reads the 8-mer table in front of the 2-bit copies
-	constexpr int FULL = TAB ? 8 : S2 ? 16 : 8; // bases the first probe of the match extension looks at
+	constexpr int FULL = TAB ? 8 : S2 ? kSeqPer : 8; // bases the first probe of the match extension looks at (one dword of the copy: sixteen at 2 bits, eight at 4)
 	constexpr bool kChain = TAB;                          // the table form: the rare tests of a chunk are marked as such, an interior chunk without a long run falls through
 	constexpr bool kGeo = TAB && band2_geo_cached(T, K, TB); // ... and the chunk's probe geometry is read from the slot's registers
 	// a test that is rarely true, for the forms that say so; a macro of this function alone (#undef behind it), written in the condition itself: the hint is lowered
@@ -843,8 +893,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 #pragma unroll
 				for (int u = 0; u < 4; ++u) {
 					const uint32_t J = (uint32_t)((u & 1) ? jB : jA), Q = (uint32_t)((u & 1) ? iqB : iqA);
-					const uint32_t ta = (u & 2) ? (J >> 18) & 0x3ffcu : (J >> 2) & 0x3ffcu;
-					const uint32_t qa = ((u & 2) ? (Q >> 20) : ((Q >> 4) & 0xfffu)) * 4u + (uint32_t)qoff;
+					// (the 4-bit form: dword (j >> 3), byte address (j >> 3) << 2 — up to 31 000 for the 62 000 bases of the span geometry: it fits the half)
+					const uint32_t ta = kNib ? ((u & 2) ? (J >> 17) & 0x7ffcu : (J >> 1) & 0x7ffcu) : (u & 2) ? (J >> 18) & 0x3ffcu : (J >> 2) & 0x3ffcu;
+					const uint32_t qa = (kNib ? ((u & 2) ? (Q >> 19) : ((Q >> 3) & 0x1fffu)) : ((u & 2) ? (Q >> 20) : ((Q >> 4) & 0xfffu))) * 4u + (uint32_t)qoff;
 					asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(tw[u]) : "v"(ta));
 					asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(qw[u]) : "v"(qa));
 				}
@@ -855,7 +906,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 					// v_alignbit uses bits 4:0 of the shift.  Bit 15 of the LOW half must not leak into a high half's shift: j never has it (j <= rj <=
 					// tl < 32767), a query index can — column 0 (the pad column, lane 0 of chunk 0) clamps to index -1
 					// (biased offsets: targets beyond 32 kb — j has a bit 15 too)
-					const uint32_t tsh = (u & 2) ? (BI ? (J >> 15) & 30u : J >> 15) : J << 1, qsh = (u & 2) ? (Q >> 15) & 30u : Q << 1;
+					// (the 4-bit form: the shift is (j & 7) * 4; bits 14 AND 15 of the low half would land in a high half's shift, and j has a bit 14 from 16 384 on: masked always)
+					const uint32_t tsh = kNib ? ((u & 2) ? (J >> 14) & 28u : J << 2) : (u & 2) ? (BI ? (J >> 15) & 30u : J >> 15) : J << 1;
+					const uint32_t qsh = kNib ? ((u & 2) ? (Q >> 14) & 28u : Q << 2) : (u & 2) ? (Q >> 15) & 30u : Q << 1;
 					cnt[u] = lead_eq2(__builtin_amdgcn_alignbit((uint32_t)(tw[u] >> 32), (uint32_t)tw[u], tsh) ^ __builtin_amdgcn_alignbit((uint32_t)(qw[u] >> 32), (uint32_t)qw[u], qsh));
 				}
 			} else {
@@ -905,9 +958,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 						for (int trip = 0; n < rm; ++trip) {
 							if (trip == 4) { open |= 1u << i; break; }
 							if (S2) {
-								const int32_t m = min(lead_eq2(seq16(tb0, j + n) ^ seq16(qoff, q + n)), 16);
+								const int32_t m = min(lead_eq2(seq16(tb0, j + n) ^ seq16(qoff, q + n)), kSeqPer);
 								n += m;
-								if (m < 16) break;
+								if (m < kSeqPer) break;
 							} else {
 								const uint32_t xa = seq4(j + n) ^ seq4(aqq + n), xb = seq4(j + n + 4) ^ seq4(aqq + n + 4);
 								if (xa | xb) { n += xa ? min(lead_eq(xa), 4) : 4 + min(lead_eq(xb), 4); break; }
@@ -926,7 +979,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 						if (!((ob >> i) & 1u)) continue; // uniform
 						const int32_t hh = __builtin_amdgcn_readlane(hv[i], src);
 						const int32_t j = hh + 1, q = c0s + i - 1 - tl + j, rm = min(tl - j, ql - q);
-						const int32_t n = S2 ? run_wave16(qoff, j, q, rm, FULL + 64, tb0) : run_wave2(j, qoff + q, rm, 40);
+						const int32_t n = S2 ? run_wave16(qoff, j, q, rm, FULL + 4 * kSeqPer, tb0) : run_wave2(j, qoff + q, rm, 40);
 						nmat[i] = lane == src ? n : nmat[i];
 					}
 				}
@@ -1115,12 +1168,12 @@ __global__ __launch_bounds__(T, band2_waves(T, K, TB)) void MWF_BAND2_KERNEL(con
 		pair_mem(A, (int32_t)blockIdx.x, pair, M);
 		constexpr bool TAB = kTabProbe && S2;
 		const int32_t toff = TAB ? A.band_lds_tab : 0; // (the table form: the probe table comes first, the 2-bit copies behind it)
-		const int32_t qoff = toff + (S2 ? ((M.tl >> 4) + 2) * 4 : ((M.tl + 3) & ~3) + 8); // both sequences start on a dword
+		const int32_t qoff = toff + (S2 ? ((M.tl >> kSeqDw) + 2) * 4 : ((M.tl + 3) & ~3) + 8); // both sequences start on a dword
 		PassResult R;
 		R.status = ST_OK, R.s = 0, R.info = 0, R.n_snap = 0, R.cells = 0;
 		if (S2) {
-			uint32_t bad = pack2bit<T>(M.ts, M.tl, toff);
-			bad |= pack2bit<T>(M.qs, M.ql, qoff);
+			uint32_t bad = kNib ? pack4bit<T>(M.ts, M.tl, toff) : pack2bit<T>(M.ts, M.tl, toff);
+			bad |= kNib ? pack4bit<T>(M.qs, M.ql, qoff) : pack2bit<T>(M.qs, M.ql, qoff);
 			// a base other than A/C/G/T: the host re-runs the pair on the byte-wise copy of this kernel
 			if (bad) sh.word[2] = 1;
 			__syncthreads();
@@ -1138,7 +1191,7 @@ __global__ __launch_bounds__(T, band2_waves(T, K, TB)) void MWF_BAND2_KERNEL(con
 		if (R.status == ST_OK) R = band2_pass<T, K, E1, E2, TB, S2, BI4, FOLD>(A, M, sh, edge_base, qoff, trace);
 		if (T == 512 && K == 4 && R.n_snap && threadIdx.x == 0 && fresh(A0).report_wide) atomicOr((unsigned int*)(fresh(A0).cig_head + 1), 1u); // (mwf_plan.cpp: PlanCache::wide_state)
 		R.n_snap = 0;
-		if (S2) M.t2 = lds2 + toff, M.q2 = lds2 + qoff; // the traceback's back-match reads the 2-bit copies in LDS
+		if (S2 && !kNib) M.t2 = lds2 + toff, M.q2 = lds2 + qoff; // the traceback's back-match reads the 2-bit copies in LDS (the 4-bit form: the image bytes in the arena)
 		if (TB && FOLD) M.tb_fwd = 1;
 		finish_pair(fresh(A0), M, (int32_t)blockIdx.x, pair, R, R.status, 0, T <= 256 ? &cig_loc : nullptr); // (block mode: the geometries of the short pairs — thousands per launch)
 	}
@@ -1236,8 +1289,10 @@ int band2_occupancy_bi2(const Penalty &p, const BandGeom &g, bool cigar);
 int launch_band2_tab(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar);
 bool band2_tab_supported(const Penalty &p, bool band_fold);
+int launch_band2_nib(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int band2_occupancy_nib(const Penalty &p, const BandGeom &g, bool cigar);
 
-#if !defined(MWF_BAND2_DEEP) && !defined(MWF_BAND2_BIASED) && !defined(MWF_BAND2_TAB)
+#if !defined(MWF_BAND2_DEEP) && !defined(MWF_BAND2_BIASED) && !defined(MWF_BAND2_TAB) && !defined(MWF_BAND2_NIB)
 // the packed kernel: (e1,e2) instantiated, sequences fit LDS (the host checks), every H lag >= 1
 bool band2_supported(const Penalty &p)
 {
@@ -1375,6 +1430,67 @@ int band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar)
 	if (four) return cigar ? occ_tab<4, true>(lds) : occ_tab<4, false>(lds);
 	return cigar ? occ_tab<3, true>(lds) : occ_tab<3, false>(lds);
 }
+#elif defined(MWF_BAND2_NIB)
+// the 4-bit form: 512 threads x 3 / 4 slots and the span geometry, (2,1), with traceback (never folded) and score-only folded / unfolded: nine kernels
+namespace {
+bool nib_geom_ok(const Penalty &p, const BandGeom &g)
+{
+	return g.nib != 0 && g.packed == 1 && g.seq2 != 0 && g.tab == 0 && g.lds_bytes > 0 && (g.block == 512 || g.block == kSpanT) && band2_nib_supported(p);
+}
+template <int T, int K, bool TB, bool FOLD>
+int launch_nib(const BatchArgs &a, int grid, int lds, hipStream_t st)
+{
+	if (lds > 48 * 1024) {
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&MWF_BAND2_KERNEL<T, K, 2, 1, TB, true, false, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+		(void)hipGetLastError();
+	}
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] band2 nib launch: wfa_band2_nib_kernel T %d K %d E1 2 E2 1 TB %d S2 1 BI4 0 FOLD %d, %d pairs, grid %d, lds %d B\n", T, K, (int)TB, (int)FOLD, (int)a.n_pairs, grid, lds);
+	hipLaunchKernelGGL((MWF_BAND2_KERNEL<T, K, 2, 1, TB, true, false, FOLD>), dim3(grid), dim3(T), lds, st, a);
+	return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+template <int T, int K>
+int launch_nib_geo(const BatchArgs &a, int grid, int lds_seq, hipStream_t st)
+{
+	const int lds = lds_seq + lds_tail<T, K, 2, 1>();
+	if (a.want_cigar) return launch_nib<T, K, true, false>(a, grid, lds, st);
+	// (the folded form under launch_variant's condition)
+	if (a.band_fold && a.pen.oe1 - a.pen.x == 2 && a.pen.oe1 < kFoldMaxLag) return launch_nib<T, K, false, true>(a, grid, lds, st);
+	return launch_nib<T, K, false, false>(a, grid, lds, st);
+}
+template <int T, int K>
+int occ_nib_geo(const Penalty &p, int lds_seq, bool cigar)
+{
+	const int lds = lds_seq + lds_tail<T, K, 2, 1>();
+	int n = 0;
+	// (the folded and the unfolded score-only form use the same registers and LDS, profiles/alpha16/band2_nib_registers.txt: the unfolded one answers for both)
+	const hipError_t e = cigar ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, 2, 1, true, true, false, false>, T, lds)
+	                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, MWF_BAND2_KERNEL<T, K, 2, 1, false, true, false, false>, T, lds);
+	(void)p;
+	return e == hipSuccess ? n : 0;
+}
+} // namespace
+
+bool band2_nib_supported(const Penalty &p) { return p.e1 == 2 && p.e2 == 1 && p.nH <= kMaxRing; }
+
+int launch_band2_nib(const BatchArgs &a0, int grid, const BandGeom &g, void *stream)
+{
+	if (!nib_geom_ok(a0.pen, g)) return -1;
+	BatchArgs a = a0;
+	a.band_lds_seq = g.lds_bytes;
+	hipStream_t st = (hipStream_t)stream;
+	if (g.block == kSpanT) return launch_nib_geo<kSpanT, kSpanK>(a, grid, g.lds_bytes, st);
+	if (g.span > 512 / 64 * 3 * 256) return launch_nib_geo<512, 4>(a, grid, g.lds_bytes, st);
+	return launch_nib_geo<kWideT, kWideK>(a, grid, g.lds_bytes, st);
+}
+
+int band2_occupancy_nib(const Penalty &p, const BandGeom &g, bool cigar)
+{
+	if (!nib_geom_ok(p, g)) return 0;
+	if (g.block == kSpanT) return occ_nib_geo<kSpanT, kSpanK>(p, g.lds_bytes, cigar);
+	if (g.span > 512 / 64 * 3 * 256) return occ_nib_geo<512, 4>(p, g.lds_bytes, cigar);
+	return occ_nib_geo<kWideT, kWideK>(p, g.lds_bytes, cigar);
+}
 #elif defined(MWF_BAND2_BIASED)
 int MWF_BAND2_CAT(launch_band2_bi, MWF_BAND2_BIASED)(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
 {
@@ -1412,6 +1528,7 @@ int launch_band2(const BatchArgs &a, int grid, const BandGeom &g0, void *stream)
 {
 	const int a_e1 = a.pen.e1, a_e2 = a.pen.e2;
 	BandGeom g = g0;
+	if (g.nib) return launch_band2_nib(a, grid, g, stream); // the 4-bit form (mwf_band2_nib.hip); no other form reads its copies
 	if (g.tab > 0) { // the table form; a geometry it refuses runs the plain form on the same sequence copies
 		const int rc = launch_band2_tab(a, grid, g, stream);
 		if (rc != -1) return rc;
@@ -1435,6 +1552,7 @@ bool band2_biased512_supported(const Penalty &p)
 int band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar)
 {
 	const int a_e1 = p.e1, a_e2 = p.e2;
+	if (g.nib) return band2_occupancy_nib(p, g, cigar);
 	if (g.tab > 0) return band2_occupancy_tab(p, g, cigar); // (0 for a geometry the table form refuses: choose_kernel then keeps the plain form)
 	if (g.packed == 2 && !(a_e1 == 2 && a_e2 == 1)) return a_e1 <= 2 ? band2_occupancy_bi1(p, g, cigar) : band2_occupancy_bi2(p, g, cigar);
 	if (a_e1 == 3) return band2_occupancy_e3(p, g, cigar);

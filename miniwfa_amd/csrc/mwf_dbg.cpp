@@ -33,10 +33,54 @@ int alphabet_scan(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint
 	return 1;
 }
 
+// The class of mwf_alphabet_class16: as above with class 3, five to sixteen distinct bytes, between 1 and 2.  sym (classes 1 and 3): the distinct bytes in
+// ascending order, the last one repeated — class 1 up to four with the other twelve 0 (alphabet_scan's four), class 3 up to sixteen.  A pair of seventeen or more is
+// left as soon as a block of 1024 bytes has shown them.  Never reads outside t[0,tl) / q[0,ql).
+int alphabet_scan16(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint8_t sym[16])
+{
+	uint64_t m[4] = {0, 0, 0, 0};
+	auto count = [&]() { return __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) + __builtin_popcountll(m[2]) + __builtin_popcountll(m[3]); };
+	memset(sym, 0, 16);
+	for (int side = 0; side < 2; ++side) {
+		const uint8_t *p = side ? q : t;
+		const size_t n = side ? ql : tl;
+		for (size_t at = 0; at < n; at += 1024) {
+			const size_t end = at + 1024 < n ? at + 1024 : n;
+			for (size_t j = at; j < end; ++j) m[p[j] >> 6] |= 1ull << (p[j] & 63u);
+			if (count() > 16) return 2;
+		}
+	}
+	constexpr uint64_t acgt = (1ull << ('A' - 64)) | (1ull << ('C' - 64)) | (1ull << ('G' - 64)) | (1ull << ('T' - 64));
+	if (!m[0] && !m[2] && !m[3] && !(m[1] & ~acgt)) return 0;
+	const int cls = count() <= 4 ? 1 : 3, fill = cls == 1 ? 4 : 16;
+	int have = 0;
+	uint8_t last = 0;
+	for (int k = 0; k < 4; ++k)
+		for (uint64_t w = m[k]; w; w &= w - 1) sym[have++] = last = (uint8_t)(64 * k + __builtin_ctzll(w));
+	for (; have < fill; ++have) sym[have] = last;
+	return cls;
+}
+
 } // namespace host
 } // namespace mwf
 
 extern "C" {
+
+int32_t mwf_alphabet_class16(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256])
+{
+	uint8_t sym[16];
+	const int cls = mwf::host::alphabet_scan16((const uint8_t*)ts, tl > 0 ? (size_t)tl : 0, (const uint8_t*)qs, ql > 0 ? (size_t)ql : 0, sym);
+	if (map) {
+		memset(map, 0, 256);
+		if (cls == 1)
+			for (int k = 0; k < 4; ++k)
+				if (k == 0 || sym[k] != sym[k - 1]) map[sym[k]] = (uint8_t)"ACGT"[k];
+		if (cls == 3)
+			for (int k = 0; k < 16; ++k)
+				if (k == 0 || sym[k] != sym[k - 1]) map[sym[k]] = (uint8_t)(MWF_ALPHA16_TAG | k);
+	}
+	return cls;
+}
 
 int32_t mwf_alphabet_class(int32_t tl, const char *ts, int32_t ql, const char *qs, uint8_t map[256])
 {

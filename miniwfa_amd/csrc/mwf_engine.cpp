@@ -99,6 +99,7 @@ int mwf_gpu_set(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "band_fold")) g->band_fold = value != 0;
 	else if (!strcmp(name, "probe_table")) g->probe_table = value != 0;
 	else if (!strcmp(name, "alpha_remap") && (value == 0 || value == 1)) g->alpha_remap = (int)value;
+	else if (!strcmp(name, "alpha16") && (value == 0 || value == 1)) g->alpha16 = (int)value;
 	else if (!strcmp(name, "trim")) { (void)hipSetDevice(g->device); trim(g); }
 	else return -1;
 	++g->tun_gen; // (whatever the tunable: no hand-kept list of "the ones that classify" to forget an entry of)
@@ -451,6 +452,9 @@ mwf_gpu_t *acquire_engine(int dev)
 	// MWF_ALPHA_REMAP=1: the engines the drop-in calls, chain mode and the dispatcher create run with "alpha_remap" 1 (include/miniwfa.h)
 	static const bool alpha = []() { const char *e = getenv("MWF_ALPHA_REMAP"); return e && !strcmp(e, "1"); }();
 	if (alpha) (void)mwf_gpu_set(g, "alpha_remap", 1);
+	// MWF_ALPHA16=1: ... with "alpha_remap" 1 and "alpha16" 1
+	static const bool alpha16 = []() { const char *e = getenv("MWF_ALPHA16"); return e && !strcmp(e, "1"); }();
+	if (alpha16) (void)mwf_gpu_set(g, "alpha_remap", 1), (void)mwf_gpu_set(g, "alpha16", 1);
 	return g;
 }
 

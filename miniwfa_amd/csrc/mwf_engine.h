@@ -93,6 +93,8 @@ struct mwf_gpu_s {
 	int seq2bit = 1;           // packed band kernel: 2-bit sequence copy in LDS for pairs of plain A/C/G/T (0: always bytes)
 	bool acgt_off_once = false; // set around the re-run of pairs that are not plain ACGT
 	int alpha_remap = 0;       // 1: pairs of at most four distinct bytes are copied into a per-batch arena with their bytes mapped onto A/C/G/T and planned as plain pairs (alpha_prepare, mwf_memory.cpp); 0: never
+	int alpha16 = 0;           // 1 (with alpha_remap 1 only): pairs of 5 to 16 distinct bytes are class 3, copied as 0x40 | code, and take the packed band kernel's 4-bit form under gap extensions (2,1)
+	bool nib_once = false;     // set around a launch whose pairs are all class 3 on the 4-bit route: choose_kernel picks the 4-bit geometries (as acgt_off_once picks the byte-wise one)
 	int64_t alpha_arena_budget = -1; // mwf_gpu_test_hook "alpha_arena_budget": bytes an arena may take (-1: four fifths of what is free) — tests of the fall-back
 	int lds_e2 = 1;            // generic kernel: keep E2/F2 in LDS where that applies (0: never)
 	int scalar_generic = 0;    // 1: the generic kernel's original one-column-per-lane pass everywhere (comparison / fallback)
@@ -153,8 +155,10 @@ struct mwf_gpu_batch_s {
 	// offsets from d_rt_off / d_rq_off: the batch's own for classes 0 and 2, the copy in the arena (as an offset from d_seqs) for class 1.
 	std::vector<int8_t> h_acgt_host; // h_acgt as the upload made it (empty: wrapped) — what h_acgt goes back to
 	std::vector<int8_t> h_alpha;    // class of every pair (mwf_alphabet_class): from the host twin while an uploaded batch was packed, from the kernel's classification at every align of a wrapped one
-	std::vector<uint32_t> h_sym;    // ... and its distinct bytes (AlphabetArgs::sym)
-	DevBuf alpha_cls;               // device: [sym: n uint32 | cls: n int8]
+	std::vector<uint32_t> h_sym;    // ... and its distinct bytes (AlphabetArgs::sym: kAlphaSymWords words per pair)
+	std::vector<int8_t> h_alpha_up; // the classes the upload's host twin found, class 3 included (empty: wrapped); h_alpha is this view under the engine's "alpha16"
+	int alpha16_laid_out = -1;      // the "alpha16" the arena was laid out for
+	DevBuf alpha_cls;               // device: [sym: n x kAlphaSymWords uint32 | cls: n int8]
 	DevBuf alpha_arena;             // device: [t_off: n int64 | q_off: n int64 | dst_t, dst_q: the copy launch's destinations, n int64 each | ids of the class-1 pairs: n int32 | 64 bytes | the copies, each sequence on a 16-byte boundary | 64 bytes]
 	const int64_t *d_rt_off = nullptr, *d_rq_off = nullptr;
 	bool alpha_known = false;       // h_alpha describes the last align (mwf_gpu_batch_alphabet)
@@ -195,7 +199,7 @@ struct mwf_gpu_batch_s {
 		// four slots, and the kernel reports whether three would have held every pair; 1: three hold this batch under these options; 2: four are needed.
 		int8_t wide_state = 0;
 		bool wide_measured = false; // this align's first launch of the class ran on four slots with the report word zeroed
-		struct GI { int32_t n = 0; int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; } gi[15];
+		struct GI { int32_t n = 0; int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; } gi[17];
 		std::vector<int8_t> cls0, flags0;
 	} plan;
 	std::vector<char> host_out;     // the fixed-size results as they came back (finalize)
@@ -250,6 +254,7 @@ mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, con
                                  const char *packed, int64_t packed_bytes, const int64_t *p_t_off, const int64_t *p_q_off);
 float estimate_divergence_device(mwf_gpu_t *g, mwf_gpu_batch_t *b);
 int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b); // "alpha_remap": classes, arena and copies of the align that is about to be planned (0 also when it fell back to the original bytes)
+int alphabet_scan16(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint8_t sym[16]); // mwf_dbg.cpp: the class of mwf_alphabet_class16 and, classes 1 and 3, the distinct bytes ascending (the last repeated up to four / sixteen)
 int alphabet_scan(const uint8_t *t, size_t tl, const uint8_t *q, size_t ql, uint8_t sym[4]); // mwf_dbg.cpp: the class of mwf_alphabet_class and, class 1, the distinct bytes ascending (the last repeated up to four)
 double sketch_divergence(int32_t hit, int32_t tot, int32_t lt); // one pair's divergence from the hits of its query's `tot` 8-mers in a target of lt bases
 extern "C" int mwf_gpu_test_hook(mwf_gpu_t *g, const char *name, int64_t value); // mwf_engine.cpp: forced kernels / geometries / failure paths for tests/ and profiles/

@@ -171,14 +171,17 @@ struct AlphabetArgs {
 	const int32_t *tl, *ql;
 	const int32_t *ids;        // the pairs of the launch, one workgroup each (null: pairs 0 .. n_pairs)
 	int32_t n_pairs;
-	int32_t mode;              // 0: classify — cls[pair] and sym[pair] are written; 1: copy — the pairs with cls[pair] == 1 are written to the arena through sym[pair]
-	int8_t *cls;               // [pair] 0: every byte is one of A C G T; 1: at most four distinct bytes (and not class 0); 2: five or more
-	uint32_t *sym;             // [pair] class 1: the distinct bytes in ascending order, lowest byte first, the last one repeated up to four (byte b maps to "ACGT"[how many of the first three are below b]); else 0
+	int32_t mode;              // 0: classify — cls[pair] and sym[pair] are written; 1: copy — the pairs with cls[pair] == 1 or 3 are written to the arena through sym[pair]
+	int32_t alpha16;           // mode 0: 1 = a pair of 5 to 16 distinct bytes is class 3 ("alpha16"); 0: class 2 like every pair of five or more
+	int8_t *cls;               // [pair] 0: every byte is one of A C G T; 1: at most four distinct bytes (and not class 0); 3 (alpha16): five to sixteen; 2: more
+	uint32_t *sym;             // [pair] kAlphaSymWords words, sixteen bytes: the distinct bytes in ascending order, lowest byte first, the last one repeated — class 1 up to four (byte b maps to
+	                           // "ACGT"[how many of the first three are below b]), the other twelve 0; class 3 up to sixteen (byte b maps to 0x40 | how many of them are below b); else 0
 	// mode 1: where the copies of the launch's k-th pair go, as offsets from `seqs` (signed: the arena is an allocation of its own) — and the per-pair offset
 	// arrays the align kernels are given with `seqs`, which the workgroup enters them in (the host filled those with the batch's own offsets)
 	const int64_t *dst_t, *dst_q;
 	int64_t *out_t_off, *out_q_off;
 };
+constexpr int kAlphaSymWords = 4;                     // words of a pair's symbol record
 int alphabet_block(int64_t max_len);                  // threads per pair for a batch whose longest pair has max_len bases of target + query
 int launch_alphabet(const AlphabetArgs &a, int block, void *stream);
 int  bigring_kernel_occupancy();                     // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
@@ -194,6 +197,7 @@ struct BandGeom {
 	int lane;         // 1: the one-wave, one-diagonal-per-lane kernel for short pairs (mwf_lane.hip): block 64, span 64, lds_bytes = rings + sequences;
 	                  // 2: the one-workgroup, one-diagonal-per-lane kernel for a few mid-size pairs (mwf_mid.hip): span = columns of its LDS rows
 	int tab;          // packed kernel, table form (mwf_band2_tab.hip): bytes of lds_bytes that hold the probe table (0: the first probe reads the 2-bit copy)
+	int nib;          // packed kernel, 4-bit form (mwf_band2_nib.hip): the sequence copy holds 4 bits per base, packed from the image bytes of pairs of 5 to 16 distinct bytes ("alpha16"); block 512 or 1024
 };
 // one pair (or a few) across the whole device: mwf_sys.hip (the per-penalty hand-off kernel of rounds 1-2, mwf_coop.hip, was removed in round 5)
 bool coop_supported(const Penalty &p);
@@ -230,6 +234,7 @@ int  launch_mid(const BatchArgs &a, int grid, int block, int lds, bool seq2, voi
 bool band2_supported(const Penalty &p);
 int  launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar);
+bool band2_nib_supported(const Penalty &p);          // the 4-bit form (mwf_band2_nib.hip, BandGeom::nib) has kernels for these penalties: gap extensions (2,1)
 bool band2_tab_supported(const Penalty &p, bool band_fold); // the table form of the first probe (mwf_band2_tab.hip, BandGeom::tab) has kernels for these penalties
 bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for the set: every set band2_supported takes
 int  band2_biased512_chunks();                       // ... and the 512-thread geometry's copy on biased offsets (8 waves x slots per wave)

@@ -383,16 +383,18 @@ mwf_gpu_batch_t *batch_from_host(mwf_gpu_t *g, int32_t n, const int32_t *tl, con
 	// the host touches every byte anyway: note which pairs the 2-bit sequence copy cannot hold, so that they never take the
 	// device round trip through ST_ALPHABET
 	// (... and of those pairs the alphabet class, mwf_alphabet_class: what "alpha_remap" needs to know at the batch's first align, when the caller's bytes are gone)
-	b->h_acgt.resize((size_t)n), b->h_alpha.assign((size_t)n, 0), b->h_sym.assign((size_t)n, 0);
+	// (... with class 3 told from class 2, mwf_alphabet_class16: whether the engine's "alpha16" asks for it is only known at the align)
+	b->h_acgt.resize((size_t)n), b->h_alpha.assign((size_t)n, 0), b->h_alpha_up.assign((size_t)n, 0), b->h_sym.assign((size_t)n * kAlphaSymWords, 0);
 	auto classify = [&](int32_t i0, int32_t i1) {
 		for (int32_t i = i0; i < i1; ++i) {
 			const uint8_t *pt = ts ? (const uint8_t*)ts[i] : (const uint8_t*)packed + p_t_off[i];
 			const uint8_t *pq = ts ? (const uint8_t*)qs[i] : (const uint8_t*)packed + p_q_off[i];
 			b->h_acgt[i] = plain_acgt(pt, (size_t)tl[i]) && plain_acgt(pq, (size_t)ql[i]) ? 1 : 0;
 			if (!b->h_acgt[i]) {
-				uint8_t sym[4] = {0, 0, 0, 0};
-				b->h_alpha[i] = (int8_t)alphabet_scan(pt, (size_t)tl[i], pq, (size_t)ql[i], sym);
-				if (b->h_alpha[i] == 1) b->h_sym[i] = (uint32_t)sym[0] | (uint32_t)sym[1] << 8 | (uint32_t)sym[2] << 16 | (uint32_t)sym[3] << 24;
+				uint8_t sym[16];
+				b->h_alpha_up[i] = (int8_t)alphabet_scan16(pt, (size_t)tl[i], pq, (size_t)ql[i], sym);
+				b->h_alpha[i] = b->h_alpha_up[i] == 3 ? 2 : b->h_alpha_up[i];
+				if (b->h_alpha_up[i] == 1 || b->h_alpha_up[i] == 3) memcpy(&b->h_sym[(size_t)i * kAlphaSymWords], sym, 16);
 			}
 		}
 	};
@@ -476,6 +478,8 @@ static void alpha_off(mwf_gpu_batch_t *b)
 // then sees classes 0 and 1 as plain pairs and class 2 as known byte-wise ones; it is dropped whenever that view changed.
 // The copies are made once for an uploaded batch and at every align of a wrapped one (its contents may have changed: a stale copy would be a wrong answer).
 // An arena that does not fit what is free leaves the batch on its own bytes, as with the tunable off (the classes are still reported).
+// With "alpha16" 1 as well, pairs of five to sixteen distinct bytes are class 3 and are copied too, their bytes mapped to 0x40 | code: the plan still sees them as
+// byte-wise pairs (h_acgt 0 — no 2-bit path), every kernel compares the image bytes verbatim, and under gap extensions (2,1) mwf_plan.cpp gives them the 4-bit band kernels.
 int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 {
 	g->alpha_timed[0] = g->alpha_timed[1] = false;
@@ -491,26 +495,32 @@ int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 	int64_t max_len = 0;
 	for (int32_t i = 0; i < n; ++i) max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
 	const int block = alphabet_block(max_len);
-	if (ensure(g, b->alpha_cls, N * 5)) return -1;
+	constexpr size_t SB = kAlphaSymWords * 4; // bytes of a pair's symbol record
+	if (ensure(g, b->alpha_cls, N * (SB + 1))) return -1;
 	AlphabetArgs a{};
 	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
-	a.sym = (uint32_t*)b->alpha_cls.p, a.cls = (int8_t*)(a.sym + N);
+	a.sym = (uint32_t*)b->alpha_cls.p, a.cls = (int8_t*)(a.sym + N * kAlphaSymWords), a.alpha16 = g->alpha16;
 	bool changed = !b->alpha_known;
+	if (b->alpha16_laid_out != g->alpha16) { // the tunable moved since the arena was laid out: other classes, other copies
+		changed = true, b->alpha_laid_out = false, b->alpha16_laid_out = g->alpha16;
+		if (b->owns_inputs)
+			for (int32_t i = 0; i < n; ++i) b->h_alpha[i] = b->h_alpha_up[i] == 3 && !g->alpha16 ? 2 : b->h_alpha_up[i];
+	}
 	if (!b->owns_inputs) {
 		a.n_pairs = n, a.mode = 0;
 		HIP_TRY(g, hipEventRecord(g->ev_alpha[0], g->stream));
 		if (launch_alphabet(a, block, g->stream)) { g->err = "kernel launch failed (alphabet classes)"; return -1; }
 		HIP_TRY(g, hipEventRecord(g->ev_alpha[1], g->stream));
 		g->alpha_timed[0] = true;
-		std::vector<char> back(N * 5);
-		if (download(g, back.data(), b->alpha_cls.p, N * 5)) return -1;
-		changed = changed || b->h_alpha.size() != N || memcmp(b->h_sym.data(), back.data(), N * 4) != 0 || memcmp(b->h_alpha.data(), back.data() + N * 4, N) != 0;
+		std::vector<char> back(N * (SB + 1));
+		if (download(g, back.data(), b->alpha_cls.p, N * (SB + 1))) return -1;
+		changed = changed || b->h_alpha.size() != N || b->h_sym.size() != N * kAlphaSymWords || memcmp(b->h_sym.data(), back.data(), N * SB) != 0 || memcmp(b->h_alpha.data(), back.data() + N * SB, N) != 0;
 		if (changed) {
-			b->h_sym.resize(N), b->h_alpha.resize(N);
-			memcpy(b->h_sym.data(), back.data(), N * 4), memcpy(b->h_alpha.data(), back.data() + N * 4, N);
+			b->h_sym.resize(N * kAlphaSymWords), b->h_alpha.resize(N);
+			memcpy(b->h_sym.data(), back.data(), N * SB), memcpy(b->h_alpha.data(), back.data() + N * SB, N);
 		}
 	} else if (!b->alpha_laid_out) {
-		if (upload_segments(g, (char*)b->alpha_cls.p, std::vector<Seg>{Seg{b->h_sym.data(), N * 4}, Seg{b->h_alpha.data(), N}})) return -1;
+		if (upload_segments(g, (char*)b->alpha_cls.p, std::vector<Seg>{Seg{b->h_sym.data(), N * SB}, Seg{b->h_alpha.data(), N}})) return -1;
 	}
 	b->alpha_known = true;
 	const bool lay_out = !b->alpha_laid_out || (!b->owns_inputs && changed);
@@ -522,7 +532,7 @@ int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 		std::vector<int32_t> ids(N, 0);
 		int64_t pos = 0;
 		for (int32_t i = 0; i < n; ++i) {
-			if (b->h_alpha[i] != 1) continue;
+			if (b->h_alpha[i] != 1 && b->h_alpha[i] != 3) continue;
 			dst[(size_t)n1] = pos, pos += (int64_t)align_up((size_t)b->h_tl[i], 16);
 			dst[N + (size_t)n1] = pos, pos += (int64_t)align_up((size_t)b->h_ql[i], 16);
 			ids[(size_t)n1++] = i;
@@ -550,7 +560,7 @@ int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 		}
 		b->alpha_laid_out = true;
 	} else {
-		for (int32_t i = 0; i < n; ++i) n1 += b->h_alpha[i] == 1;
+		for (int32_t i = 0; i < n; ++i) n1 += b->h_alpha[i] == 1 || b->h_alpha[i] == 3;
 	}
 	if (n1 > 0 && (lay_out || !b->owns_inputs)) {
 		char *base = (char*)b->alpha_arena.p;
@@ -569,7 +579,7 @@ int alpha_prepare(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 	b->d_rq_off = n1 > 0 ? (const int64_t*)b->alpha_arena.p + N : b->d_q_off;
 	if (!b->alpha_active || changed) {
 		b->h_acgt.resize(N);
-		for (int32_t i = 0; i < n; ++i) b->h_acgt[i] = b->h_alpha[i] != 2;
+		for (int32_t i = 0; i < n; ++i) b->h_acgt[i] = b->h_alpha[i] == 0 || b->h_alpha[i] == 1; // (class 3 stays a byte-wise pair: no 2-bit path is ever planned for it)
 		b->plan.valid = false;
 	}
 	b->alpha_active = true;

@@ -119,16 +119,18 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 		pl.kind = 0, pl.band = BandGeom{0, 0, 0, 0, 0, 0}, geom_block = 1024;
 	}
 	if (geom_block == 1024) { // the span geometry (the caller checked the lengths of every pair: kBandSpanMaxSeq); 2-bit sequence copies only
-		const int64_t need_lds = ((max_len >> 4) + 4) * 4;
+		// ("alpha16", a launch of class-3 pairs: 4-bit copies — eight bases per dword, 62 000 bases per sequence about 62 KB)
+		const bool nib = g->nib_once && band2_nib_supported(P);
+		const int64_t need_lds = nib ? ((max_len >> 3) + 4) * 4 : ((max_len >> 4) + 4) * 4;
 		if (g->band_span == 0 || g->seq2bit == 0 || g->acgt_off_once || need_lds > 150 * 1024) return;
-		pl.kind = 2, pl.band = BandGeom{1024, 1, (int)band2_span_chunks() * 256, (int)((need_lds + 15) / 16 * 16), 1, 0};
+		pl.kind = 2, pl.band = BandGeom{1024, 1, (int)band2_span_chunks() * 256, (int)((need_lds + 15) / 16 * 16), 1, 0, 0, nib ? 1 : 0};
 		return;
 	}
 	// (window_hint: pairs a kernel handed back early come with the window they are expected to need, dev::window_forecast — the re-run
 	// takes the class that fits that, not the one that fits the worst case)
 	const int64_t max_window = window_hint > 0 ? std::min<int64_t>(std::min<int64_t>(max_len + 1, 2 * max_bound + 3), window_hint) : std::min<int64_t>(max_len + 1, 2 * max_bound + 3);
 	BandGeom bg;
-	bg.packed = 0, bg.seq2 = 0, bg.lane = 0, bg.tab = 0;
+	bg.packed = 0, bg.seq2 = 0, bg.lane = 0, bg.tab = 0, bg.nib = 0;
 	// Packed variants (E/F registers as int16 pairs): valid when no offset (a target index, plus at most one per penalty for
 	// offsets that ran past the matrix) and no penalty count can reach 32767.  They halve the state registers, which is
 	// what lets several workgroups share a CU — one pair's barrier phase then overlaps another's compute:
@@ -151,6 +153,9 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	if (g->block == 64 || g->block == 128 || g->block == 256 || g->block == 512 || g->block == 768) bg.block = g->block;
 	// geometry picked by the caller for a size class (pairs short enough that their window should stay inside a small span)
 	if (g->block == 0 && (geom_block == 64 || geom_block == 128 || geom_block == 256)) bg.block = geom_block;
+	// "alpha16", a launch of class-3 pairs: the 4-bit form exists on the 512-thread geometry (three or four slots) whatever the window class (a forced 768 stays byte-wise)
+	const bool nib = g->nib_once && g->seq2bit != 0 && !g->acgt_off_once && band2_nib_supported(P) && bg.block != 768;
+	if (nib) bg.block = 512;
 	bg.span = bg.block / 64 * (bg.block != 768 ? 3 : 2) * 256;
 	// (a forced 512-thread block with "wide_slots" 4: four slots whatever the window — tests of the four-slot kernels on short pairs)
 	const bool four_slots = bg.block == 512 && ((g->block == 0 && window_hint > kBandWideWindow && window_hint <= kBandWide4Window) || (g->block == 512 && g->wide_slots == 4));
@@ -160,7 +165,7 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	// the packed kernel's sequence copy holds 2 bits per base unless that is switched off (or this is the re-run of pairs that
 	// are not plain ACGT): a quarter of the LDS, half the LDS instructions per probe
 	const bool seq2 = g->seq2bit != 0 && !g->acgt_off_once;
-	const int64_t need_lds = seq2 ? ((max_len >> 4) + 4) * 4 : max_seq_lds;
+	const int64_t need_lds = nib ? ((max_len >> 3) + 4) * 4 : seq2 ? ((max_len >> 4) + 4) * 4 : max_seq_lds;
 	bg.lds_bytes = need_lds <= lds_cap ? (int)((need_lds + 15) / 16 * 16) : 0;
 	bg.seq2 = seq2 && bg.lds_bytes > 0;
 	// byte-wise copy (pairs outside plain ACGT) with wide windows: three slots of state plus six probe words per column do not fit the 128
@@ -174,12 +179,13 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 		bg.lds_bytes = max_seq_lds <= 140 * 1024 ? (int)((max_seq_lds + 15) / 16 * 16) : 0;
 	}
 	if (bg.lds_bytes == 0) return; // the packed kernel keeps the sequences in LDS: what does not fit takes the generic kernel
+	bg.nib = nib && bg.seq2 && bg.block == 512; // (4-bit copies that do not fit the cap: the byte-wise geometry above)
 	pl.kind = 2, pl.band = bg;
 	// The table form (mwf_band2_tab.hip): the 512-thread geometry on 2-bit copies, default gap extensions, folded — the first probe of the match extension reads
 	// per-position 8-mer tables, one halfword per base of target and query (plus 258 entries of slack) in front of the 2-bit copies.  Worth its LDS only while two
 	// workgroups share a CU: the kernel is asked with the launch's real LDS size (a 10 kb pair: 40.7 KB of table + 5 KB of copies + 5.2 KB of bookkeeping words and edge table); otherwise the plain form, wfa_band2_kernel.
 	// (the budget only spares the query: a CU's 160 KB over two workgroups, less 6 KB for the bookkeeping words and the edge table — 5.2 KB on four slots; cached_occupancy decides)
-	if (g->probe_table && bg.block == 512 && bg.seq2 && band2_tab_supported(P, g->band_fold)) {
+	if (g->probe_table && bg.block == 512 && bg.seq2 && !bg.nib && band2_tab_supported(P, g->band_fold)) {
 		const int64_t tab = (2 * (max_len + 258) + 15) / 16 * 16;
 		const int64_t budget = g->probe_table_lds > 0 ? g->probe_table_lds : (160 / 2 - 6) * 1024;
 		if (tab + bg.lds_bytes <= budget) {
@@ -196,7 +202,7 @@ int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_
 	uint64_t key;
 	if (pl.kind == 2)
 		key = 1ull | (uint64_t)pl.band.block << 4 | (uint64_t)(pl.band.packed == 1) << 16 | (uint64_t)(pl.band.packed == 2) << 15 | (uint64_t)(pl.band.lds_bytes > 0) << 17 | (uint64_t)pl.cigar << 18 |
-		      (uint64_t)(pl.band.seq2 != 0) << 3 | (uint64_t)(pl.band.lane == 1) << 2 | (uint64_t)(pl.band.block == 512 && pl.band.span > 6144) << 1 | (uint64_t)(pl.band.block == 512 ? pl.band.span / 2048 : 0) << 56 | (uint64_t)(pl.band.lane == 2) << 19 | (uint64_t)P.e1 << 20 | (uint64_t)P.e2 << 28 | (uint64_t)pl.band.lds_bytes << 36 | (uint64_t)(pl.band.tab > 0) << 62;
+		      (uint64_t)(pl.band.seq2 != 0) << 3 | (uint64_t)(pl.band.lane == 1) << 2 | (uint64_t)(pl.band.block == 512 && pl.band.span > 6144) << 1 | (uint64_t)(pl.band.block == 512 ? pl.band.span / 2048 : 0) << 56 | (uint64_t)(pl.band.lane == 2) << 19 | (uint64_t)P.e1 << 20 | (uint64_t)P.e2 << 28 | (uint64_t)pl.band.lds_bytes << 36 | (uint64_t)(pl.band.tab > 0) << 62 | (uint64_t)(pl.band.nib != 0) << 63;
 	else key = 2ull | (uint64_t)pl.block << 4 | (uint64_t)stream_pass << 16 | (uint64_t)ring16 << 17 | (uint64_t)(P.nH > kMaxRing) << 18 | (uint64_t)lds_e2_cols << 20;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;
@@ -812,18 +818,24 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	// 10: short pairs on the one-diagonal-per-lane kernel (mwf_lane.hip); what outgrows its 64 columns moves to the band classes
 	// 11: mid-size pairs of a small batch on the one-workgroup-per-pair, rings-in-LDS kernel (mwf_mid.hip); what outgrows its span moves to the band classes
 	typedef mwf_gpu_batch_t::PlanCache::GI GroupInfo;
-	GroupInfo gi[15];
+	GroupInfo gi[17];
 	bool mid_bytes = false;
+	// ("alpha16", gap extensions (2,1)) 15: the class-3 pairs of classes 1-4 on the 4-bit 512-thread geometry, 16: those of classes 13 and 14 on the 4-bit span geometry
+	// (mwf_band2_nib.hip); hand-backs as for the plain pairs of their h_class — window overflow to the next 4-bit geometry, then the generic kernel
+	auto nib_pair = [&](int32_t i) {
+		return g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(P0) && !low_mem &&
+		       (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3;
+	};
 	// (12: the pairs of class 10 the host knows not to be plain A/C/G/T — reads with an N —: the lane kernel on byte-wise copies)
 	// 13: pairs too long (or with windows too wide) for the 512-thread packed geometry on its 1024-thread span geometry: targets of up to ~60 kb on biased
 	// 16-bit offsets, windows of up to ~16 000 columns; what outgrows it moves to the generic kernel
 	// 14: pairs of up to ~21 kb per sequence whose worst-case penalty rules out plain 16-bit offsets: the 512-thread geometry with five or six chunk slots, which computes on
 	// biased offsets with range checks like the span geometry but keeps two pairs per CU (windows of up to 9920 / 11 968 columns; what outgrows them moves to the span geometry).
 	// Built for every set the band kernel takes (band2_biased512_supported): where e2 == 2 — main.c's -a preset — the class starts at ~6.6 kb, 1024 x 10 kb batches are its.
-	static const int run_order[15] = {5, 0, 13, 14, 1, 6, 2, 7, 3, 8, 4, 9, 11, 10, 12}; // largest workspace first
+	static const int run_order[17] = {5, 0, 13, 14, 16, 1, 15, 6, 2, 7, 3, 8, 4, 9, 11, 10, 12}; // largest workspace first
 	if (PC.has_groups) { // same lengths, same options, same tunables as last time: classes, order (already on the device) and maxima as they were
 		b->h_class = PC.cls0, b->h_flags = PC.flags0;
-		for (int c = 0; c < 15; ++c) gi[c] = PC.gi[c];
+		for (int c = 0; c < 17; ++c) gi[c] = PC.gi[c];
 		mid_bytes = PC.mid_bytes;
 	} else {
 		const bool lane_ok = g->lane_max_len > 0 && lane_supported(P0);
@@ -836,7 +848,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		const bool know_acgt = !b->h_acgt.empty() && g->seq2bit != 0;
 		const bool pack_pen = g->band_pack != 0 && band2_supported(P0);
 		std::vector<int8_t> cls((size_t)b->n); // group of every pair
-		int32_t count[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		int32_t count[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		const bool span_pen = pack_pen && g->band_span != 0 && g->seq2bit != 0;
 		// The classes' length limits stand for "the window stays inside the span at ~5 % divergence".  Where the batch's own divergence is known
 		// (estimate_divergence: batches built from host memory) the lengths are weighed by it: three times as diverged = as if three times as long.
@@ -886,7 +898,8 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 				// the unpacked band kernel and no window overflows to re-run, see choose_kernel)
 				// (... unless the span geometry of the packed kernel takes it: windows of up to ~16 000 columns — a 50 kb pair at 3 % —, which is
 				// where the pairs whose windows will mostly fit are drawn: tl + ql below seven spans; bench.py long_batches)
-				const bool span_ok = span_pen && tl <= kBandSpanMaxSeq && ql <= kBandSpanMaxSeq && !(know_acgt && !b->h_acgt[i]);
+				const bool nib_i = nib_pair(i); // (its 4-bit copy stands where a plain pair's 2-bit copy does: the long classes admit it)
+				const bool span_ok = span_pen && tl <= kBandSpanMaxSeq && ql <= kBandSpanMaxSeq && (!(know_acgt && !b->h_acgt[i]) || nib_i);
 				if (span_ok && g->band_span == 2) c = 13;
 				// (round 5: the limits leave the mean window at 5 % — 0.27 (tl+ql) — a quarter of margin below each class's widest window; round 4's left 4-18 %,
 				// and 2 kb pairs, just inside the 128-thread class, were re-run at 7.8 %: profiles/r04/chooser_regression.txt)
@@ -941,7 +954,8 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 					}
 				}
 			}
-			if (c >= 1 && c <= 4 && know_acgt && !b->h_acgt[i] && packable) c += 5;
+			if (((c >= 1 && c <= 4 && packable) || c == 13 || c == 14) && nib_pair(i)) c = c <= 4 ? 15 : 16;
+			else if (c >= 1 && c <= 4 && know_acgt && !b->h_acgt[i] && packable) c += 5;
 			return c;
 		};
 		for (int32_t i = 0; i < b->n; ++i) cls[(size_t)i] = (int8_t)classify(i, mid_ok);
@@ -965,7 +979,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		// The processing order: groups in run order, longest first inside a group (the persistent workgroups finish together; the classes on the shared
 		// work counter then by predicted work, below).  h_order is
 		// already sorted longest first (batch_common) and that order is stable: one pass over it deals the pairs to their groups.
-		std::vector<int32_t> start(15, 0), order((size_t)b->n);
+		std::vector<int32_t> start(17, 0), order((size_t)b->n);
 		{
 			int32_t at = 0;
 			for (int c : run_order) start[c] = at, at += count[c], gi[c].n = count[c];
@@ -984,7 +998,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		// The estimate: s ~ (tl + ql) x d, d from the share of the query's 8-mers found in the target over the WHOLE pair (correlation 0.88 with s;
 		// the batch sketch's 1500-base prefix 0.34).  A class that fits on the device at once (no more pairs than workgroups) has nothing to deal.
 		bool reorder = false;
-		for (int c : {13, 14, 1, 6}) reorder |= count[c] > 2 * g->n_cu; // (two workgroups per CU on the 512-thread geometries; the span geometry holds fewer)
+		for (int c : {13, 14, 16, 1, 15, 6}) reorder |= count[c] > 2 * g->n_cu; // (two workgroups per CU on the 512-thread geometries; the span geometry holds fewer)
 		if (reorder && g->work_order != 0 && (g->work_order != 2 || (int32_t)b->h_iter.size() == b->n)) {
 			const int32_t lo = start[13] - count[13], hi = start[6]; // (run_order keeps the four side by side)
 			std::vector<double> key((size_t)b->n, 0.0);
@@ -1004,7 +1018,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 			} else if (g->work_order == 2) {
 				for (int32_t k = lo; k < hi; ++k) key[(size_t)order[(size_t)k]] = (double)b->h_iter[(size_t)order[(size_t)k]];
 			}
-			for (int c : {13, 14, 1, 6}) {
+			for (int c : {13, 14, 16, 1, 15, 6}) {
 				if (count[c] <= 2 * g->n_cu) continue;
 				const auto first = order.begin() + (start[c] - count[c]), last = order.begin() + start[c];
 				if (g->work_order == 3) std::reverse(first, last); // (shortest first: the other bound of the measurement)
@@ -1020,7 +1034,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 			if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{b->h_order.data(), b->h_order.size() * 4}})) return -1; // (waits for earlier work on the stream first)
 		}
 		PC.cls0 = b->h_class, PC.flags0 = b->h_flags, PC.mid_bytes = mid_bytes, PC.has_groups = true;
-		for (int c = 0; c < 15; ++c) PC.gi[c] = gi[c];
+		for (int c = 0; c < 17; ++c) PC.gi[c] = gi[c];
 	}
 	int n_groups = 0, done_groups = 0;
 	for (const GroupInfo &G : gi) n_groups += G.n > 0;
@@ -1032,18 +1046,24 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		if (G.n == 0) continue;
 		++done_groups;
 		int ran = 0;
-		const int cc = c == 14 ? 8 : c == 13 ? 7 : c == 11 ? 6 : (c == 10 || c == 12) ? 5 : c > 5 ? c - 5 : c;
+		const int cc = c == 16 ? 7 : c == 15 ? 1 : c == 14 ? 8 : c == 13 ? 7 : c == 11 ? 6 : (c == 10 || c == 12) ? 5 : c > 5 ? c - 5 : c;
 		// (the lane class of a batch of reads hands its overflows to a follow-up launch on the device, below)
 		const bool lane_retry = (c == 10 || c == 12) && g->dev_retry && G.n >= 1024 && !preset && g->force_kind < 0 && g->block == 0 && mid_supported(P0) && G.max_len <= 1200 &&
 		                        G.max_tl + G.max_bound < 32760 && !low_mem;
 		if (lane_retry) g->retry_mode = 1, g->retry_slot = c == 12 ? 1 : 0;
 		g->acgt_off_once = (c > 5 && c < 10) || (c == 11 && mid_bytes) || c == 12;
+		// (a forced kernel or block keeps the batch in one group: the 4-bit form then only where every pair of it is class 3)
+		bool all_nib = !classes && c == 0 && g->force_kind != 0;
+		for (int32_t i = 0; all_nib && i < b->n; ++i) all_nib = nib_pair(i);
+		g->nib_once = c == 15 || c == 16 || all_nib;
+		const bool wide_c = c == 1 || c == 15; // the classes on the 512-thread geometry of three or four slots
 		const int rc = run_batch_kernel(g, b, c == 5 ? *opt : opt_hi, b->d_order + at, G.n, slots, G.max_len, G.max_bound, G.max_bound1,
 		                                done_groups == 1, (classes || c >= 11) ? (c == 0 || c == 5 ? 0 : 2) : -1, G.max_tl, G.max_seq_lds, lane_retry ? 0 : done_groups == n_groups,
 		                                cc == 8 ? 514 : cc == 7 ? 1024 : cc == 6 ? 33 : cc == 5 ? 32 : cc == 4 ? 64 : cc == 3 ? 128 : cc == 2 ? 256 : 0, &ran,
-		                                (c == 1 && (g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean))) ? kBandWide4Window : (c == 14 || c == 11) ? G.max_exp_win : 0);
+		                                (wide_c && (g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean))) ? kBandWide4Window : (c == 14 || c == 11) ? G.max_exp_win : 0);
 		g->retry_mode = 0;
-		if (c == 1 && g->wide_slots == 0 && PC.wide_state == 0 && g->queue_clean && ran == 2 && g->stats.block == 512) PC.wide_measured = true;
+		g->nib_once = false;
+		if (wide_c && g->wide_slots == 0 && PC.wide_state == 0 && g->queue_clean && ran == 2 && g->stats.block == 512) PC.wide_measured = true;
 		// Batches of reads: what the lane kernel hands back (a window that left its chunks: one read in tens of thousands) is re-run by a follow-up launch of
 		// the mid kernel, whose span holds the widest window such a pair can have — from a list the lane kernel filled ON THE DEVICE.  Round 4 read the status
 		// words back, launched, waited and read them again: ~0.2 ms behind a 0.5 ms launch.  (An empty list costs the launch of a few idle workgroups.)
@@ -1064,7 +1084,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		g->acgt_off_once = false;
 		if (rc) return -1;
 		// (bit 64: the pair ran on the plain three-slot 512-thread geometry — the only one whose LATE overflow says "this batch's wide class needs four slots")
-		const bool three_slots = c == 1 && ran == 2 && g->stats.block == 512 && !(g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean));
+		const bool three_slots = wide_c && ran == 2 && g->stats.block == 512 && !(g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean));
 		for (size_t j = at; j < at + (size_t)G.n; ++j) {
 			const int32_t i = b->h_order[j];
 			b->h_kind[i] = (int8_t)ran, b->h_flags[i] = (int8_t)((b->h_flags[i] & ~64) | (three_slots ? 64 : 0));
@@ -1237,7 +1257,12 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 		const bool shrink = !same_fewer[0][0].empty() || !same_fewer[0][1].empty() || !same_fewer[2][0].empty() || !same_fewer[2][1].empty();
 		if (shrink) tb_slots = std::max(1, tb_slots / 8);
 		auto pl_low_mem = [](const mwf_opt_t &o) { return (o.flag & MWF_F_CIGAR) && o.step > 0; };
-		auto rerun = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast = false, int geom = 0) -> int {
+		const Penalty Pn = make_penalty(b->opt);
+		auto nib_pair = [&](int32_t i) { // (as the plan's: the pair's copy holds image bytes and the set has 4-bit kernels — a re-run respects the class)
+			return g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(Pn) && !pl_low_mem(b->opt) &&
+			       (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3;
+		};
+		auto rerun1 = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast, int geom, bool nib) -> int {
 			if (ids.empty()) return 0;
 			int64_t hint = 0;
 			if (use_forecast) { // every pair of the re-run came back with a forecast: the class that holds the widest of them (+ 25 %)
@@ -1267,14 +1292,24 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 			// of band kernel in every align of the 40 000-pair batch, profiles/r04/rocprof_lane_kernel_40000x150bp.txt)
 			const Penalty Pm = make_penalty(o);
 			const int mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
-			const bool to_mid = want_kind == 2 && use_forecast && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(Pm) && max_len <= 1200 &&
+			const bool to_mid = want_kind == 2 && use_forecast && !nib && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(Pm) && max_len <= 1200 &&
 			                    max_tl + max_bound < 32760 && !(pl_low_mem(o));
+			g->nib_once = nib;
 			if (rc == 0) rc = run_batch_kernel(g, b, o, (const int32_t*)tmp.p, (int32_t)ids.size(), slots, max_len, max_bound, max_bound1, false,
 			                                   want_kind, max_tl, max_seq_lds, 0, to_mid ? 33 : geom, &ran, hint);
+			g->nib_once = false;
 			if (rc == 0) rc = hipStreamSynchronize(g->stream) == hipSuccess ? 0 : -1;
 			if (rc) return -1;
 			for (int32_t i : ids) b->h_kind[i] = (int8_t)ran;
 			return 0;
+		};
+		// a band re-run on sequence copies: the class-3 pairs of the list ("alpha16") apart from the rest, on the 4-bit form of the same geometry
+		auto rerun = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast = false, int geom = 0) -> int {
+			if (want_kind != 2 || g->acgt_off_once || pl_low_mem(step0 ? opt_hi : b->opt)) return rerun1(ids, step0, want_kind, slots, use_forecast, geom, false);
+			std::vector<int32_t> nib_ids, rest;
+			for (int32_t i : ids) (nib_pair(i) ? nib_ids : rest).push_back(i);
+			if (rerun1(rest, step0, want_kind, slots, use_forecast, geom, false)) return -1;
+			return rerun1(nib_ids, step0, want_kind, slots, use_forecast, geom, true);
 		};
 		const int wide = 1 << 30;
 		for (int z = 0; z < 2; ++z) {
