@@ -488,9 +488,11 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		r.N2 = *(const int32_t*)(r2 + noff);
 		if (!FOLD) r.O1 = *(const int2*)(r1 + off), r.N1 = *(const int32_t*)(r1 + noff);
 	};
-	int64_t cells = 0, tb_used = 0;
-	int32_t est_window = 0;
 	const int64_t iter_limit = A.max_iter > 0 ? A.max_iter : INT64_MAX;
+	// (kChain: `cells` holds what is LEFT of the iteration budget, iter_limit less the cells computed, and the test behind the barrier is its sign — the limit itself was
+	// reloaded from the kernarg segment at every penalty, a scalar-memory round trip on every wave's path between two penalties; R.cells is rebuilt at the exit)
+	int64_t cells = kChain ? iter_limit : 0, tb_used = 0;
+	int32_t est_window = 0;
 	const int32_t s_limit = A.max_s > 0 ? A.max_s : INT32_MAX;
 	const int64_t rows_slot = TB ? A.rows_slot : 0, tb_slot_bytes = TB ? A.tb_slot_bytes : 0;
 
@@ -526,7 +528,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	// is only kept when nothing else is in motion: no slot ageing, no remap pending (gl_next == gl, up_wait == 0), the coarse overflow and
 	// three-slot tests false, i.e. false for every window with these chunks.  Every other penalty runs the full header.
 	// est: per slot k bits 4k..4k+3 = runs | holds the lo edge (g == ga) | holds the hi edge (g == gb) | ageing (outside the window);
-	// bit 24 / 25: this wave stores the dead chunk below / above the window.
+	// bit 24 / 25: this wave stores the dead chunk below / above the window;
+	// kChain, bit 26 + k: slot k runs the chunk that holds column ql + 1, the only one the end cell can lie in (a function of gk[k], which a remap alone changes — and
+	// a remap drops the key).
 	int32_t ekey = 0;
 	// Gated off, i.e. the full header every penalty: the span geometry (the cached word costs its folded score-only form its last free register — scratch where it had
 	// none) and the 64-thread geometry (one wave per pair: nothing is repeated eight times, and 2048 x 400 bp measured 0.366 -> 0.404 ms with the fast header).
@@ -534,6 +538,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	uint32_t est = 0;
 	static_assert(kEpoch || ((NW & (NW - 1)) == 0 && !(T == 512 && K == 4)), "the full header of the gated geometries is written for a power-of-two wave count and no three-slot note");
 	static_assert(K <= 6, "slot classes of the window epoch: four bits per slot below bit 24");
+	constexpr bool kLeanTail = kChain; // the table form: the rare work behind a chunk's extension hangs on bits of est alone
+	static_assert(!kLeanTail || (kEpoch && K <= 4), "the table form keeps one more bit per slot in est, from bit 26 on");
+	constexpr uint32_t kRunBits = 0x111111u & ((1u << (4 * K)) - 1u); // the "runs" bit of every slot
 
 	// One penalty; returns true when the pass ends.  A depth-2 history is two registers, [0] the newer: the penalty reads [1] for the last
 	// time, overwrites it, and the two trade places (v_swap_b32) — no copies, and a slot that is skipped leaves its registers alone.
@@ -595,6 +602,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 				if ((uint32_t)(gk[k] - ga) <= (uint32_t)gspan) {
 					idle[k] = 0;
 					st |= (1u | (gk[k] == ga ? 2u : 0u) | (gk[k] == gb ? 4u : 0u)) << (4 * k);
+					if (kLeanTail && (uint32_t)(ql + 1 - gk[k] * kChunk) < (uint32_t)kChunk) st |= 1u << (26 + k);
 					if (k < 2 || k == K - 1) ++n_busy;
 				} else if (idle[k] < kAgeOut) {
 					++idle[k];
@@ -827,6 +835,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 					if (__ballot(any != 0)) bits |= 0x80u;
 				}
 			}
+			if (kLeanTail && bits != 0 && lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits); // (bits is uniform)
 			} // special
 			// ---- the new E/F are final: age the registers, publish this chunk's outer columns for the neighbouring slots
 			if (FOLD) { // with the row read for the mismatch term: what the gap opens from e1 penalties from now (HX is not masked: it is dead outside ITS window)
@@ -990,15 +999,25 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- termination test of the extension sweep (miniwfa.c:405-409): only column ql+1 can hold the end cell
 			unsigned long long fm = 0;
 			int32_t done_info = 0;
-			if (MWF_RARE((uint32_t)(cfin - cb) < (uint32_t)kChunk && cfin >= lo && cfin <= hi)) { // uniform
+			// (kChain: two levels — the slot's bit in est says that the chunk holds the column at all, and only such a chunk compares it with the window: one bit test
+			// on every other chunk's path instead of three compares)
+			bool end_bit = false;
+			if constexpr (kLeanTail) end_bit = MWF_RARE((st & (1u << (26 + k))) != 0) && cfin >= lo && cfin <= hi;
+			if (MWF_RARE(kLeanTail ? end_bit : (uint32_t)(cfin - cb) < (uint32_t)kChunk && cfin >= lo && cfin <= hi)) { // uniform
 				const int32_t rel = cfin - cb, hi_half = (rel >> 1) & 1;
 				const int32_t hv = half_of((rel & 1) ? hxB : hxA, hi_half) + B, nm = (int32_t)((uint32_t)((rel & 1) ? nmB : nmA) >> (hi_half ? 16 : 0) & 0xffffu);
 				const uint32_t f = (uint32_t)(lane == (rel >> 2)) & (uint32_t)(hv == tl - 1) & inm_bit(ql - tl, hv - nm, tl, ql);
 				done_info = (f && nm == 0) ? (int32_t)((tbw >> (8 * (rel & 3))) & 7u) : 0;
 				fm = __ballot(f != 0);
+				// (kChain: the flag word gets the end cell's bits here and a window edge's in the block above — the only places they can come from — so that a chunk
+				// that is neither tests nothing behind its store)
+				if (kLeanTail && fm) {
+					const uint32_t fin = 4u | (uint32_t)__builtin_amdgcn_readlane(done_info, (int32_t)__builtin_ctzll(fm)) << 4;
+					if (lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], fin);
+				}
 			}
 			*(int2*)(rown + off) = make_int2(hxA, hxB);
-			++n_stores;
+			if (!kLeanTail) ++n_stores;
 #if MWF_B2_TIMING == 2
 			if (timed) {
 				asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc4) : "v"(hxA), "v"(hxB) : "memory");
@@ -1015,11 +1034,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 					if (lane == 0) gword[i] = m;
 				}
 			}
-			if (fm) bits |= 4u | (uint32_t)__builtin_amdgcn_readlane(done_info, (int32_t)__builtin_ctzll(fm)) << 4;
-			if (kChain) { // (bits is uniform: a scalar test that falls through instead of an exec mask and a taken branch)
-				if (MWF_RARE(bits != 0))
-					if (lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
-			} else if (bits && lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
+			if (!kLeanTail) {
+				if (fm) bits |= 4u | (uint32_t)__builtin_amdgcn_readlane(done_info, (int32_t)__builtin_ctzll(fm)) << 4;
+				if (kChain) { // (bits is uniform: a scalar test that falls through instead of an exec mask and a taken branch)
+					if (MWF_RARE(bits != 0))
+						if (lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
+				} else if (bits && lane == 0) atomicOr((unsigned int*)&sh.flags[npar][0], bits);
+			}
 		}
 
 		if (forecast) {
@@ -1033,9 +1054,12 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		const uint64_t tm2 = __builtin_readcyclecounter();
 #endif
 		// the coming penalty: its rows, and the request for the first active chunk's (five loads, younger than every store)
-		bn = bn + RS == ring_bytes ? 0u : bn + RS, bx = bx + RS == ring_bytes ? 0u : bx + RS;
-		b1 = b1 + RS == ring_bytes ? 0u : b1 + RS, b2 = b2 + RS == ring_bytes ? 0u : b2 + RS;
-		const bool young_store = relaxed_stores && n_stores > 0 && !TB && !track_good;
+		if constexpr (!kChain) { // (kChain: behind the barrier, while the flag word is on its way)
+			bn = bn + RS == ring_bytes ? 0u : bn + RS, bx = bx + RS == ring_bytes ? 0u : bx + RS;
+			b1 = b1 + RS == ring_bytes ? 0u : b1 + RS, b2 = b2 + RS == ring_bytes ? 0u : b2 + RS;
+		}
+		// (the table form: "some slot of this wave stored a row" is a function of the slot classes — a chunk that runs stores — not a counter kept by every chunk)
+		const bool young_store = relaxed_stores && (kLeanTail ? (st & kRunBits) != 0 : n_stores > 0) && !TB && !track_good;
 		if (young_store) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
 		else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #ifdef MWF_B2_TIMING
@@ -1045,7 +1069,16 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 		asm volatile("" ::: "memory");
 
 		// ---- bookkeeping, identical on every thread
-		const uint32_t fl = (uint32_t)uni(sh.flags[npar][0]);
+		// (kChain: the read of the flag word is issued here and waited for behind everything that does not depend on it — the row offsets, the penalty's counters, the
+		// edge-table rotation, the slot mapping; the wait stood one instruction behind the read, a whole LDS round trip on every wave's path behind the barrier)
+		uint32_t fl = 0;
+		int32_t flv = 0;
+		if constexpr (kChain) {
+			static_assert(!kChain || !BI, "the range checks of the biased offsets leave before the penalty turns");
+			asm volatile("ds_read_b32 %0, %1" : "=v"(flv) : "v"((uint32_t)(uintptr_t)&sh.flags[npar][0]) : "memory");
+			bn = bn + RS == ring_bytes ? 0u : bn + RS, bx = bx + RS == ring_bytes ? 0u : bx + RS;
+			b1 = b1 + RS == ring_bytes ? 0u : b1 + RS, b2 = b2 + RS == ring_bytes ? 0u : b2 + RS;
+		} else fl = (uint32_t)uni(sh.flags[npar][0]);
 #ifdef MWF_B2_TIMING
 		if (trace_band && tid == (fresh(A).max_iter < 0 ? (int32_t)-fresh(A).max_iter : 0) && s_new - 1 < fresh(A).dbg_cap) { // cycles: header | chunks, drain | barrier+flags; chunks this wave ran in bits 28..
 			const uint64_t tm4 = __builtin_readcyclecounter();
@@ -1059,10 +1092,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 #endif
 		}
 #endif
-		if (fl & 1u) wf_lo = lo;
-		if (fl & 2u) wf_hi = hi;
-		const int32_t done = (int32_t)((fl >> 2) & 1u), payload = (int32_t)((fl >> 4) & 7u);
-		if (BI && (fl & 0x80u)) { R.status = ST_BAND_OVERFLOW; return true; } // a value came near the end of its 16-bit range (wide_bias)
+		int32_t done = 0, payload = 0;
+		if constexpr (!kChain) {
+			if (fl & 1u) wf_lo = lo;
+			if (fl & 2u) wf_hi = hi;
+			done = (int32_t)((fl >> 2) & 1u), payload = (int32_t)((fl >> 4) & 7u);
+			if (BI && (fl & 0x80u)) { R.status = ST_BAND_OVERFLOW; return true; } // a value came near the end of its 16-bit range (wide_bias)
+		}
 		s = s_new, curH = newH, par = npar;
 		{
 			const int32_t oldest = epos[D - 1];
@@ -1085,6 +1121,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			} else up_wait = 0, ekey = ~ekey; // (-1, nothing to keep, becomes 0: no key)
 		}
 		if (TB) tb_used += row_bytes;
+		if constexpr (kChain) {
+			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(flv));
+			fl = (uint32_t)__builtin_amdgcn_readfirstlane(flv);
+			if (fl & 1u) wf_lo = lo;
+			if (fl & 2u) wf_hi = hi;
+			done = (int32_t)((fl >> 2) & 1u), payload = (int32_t)((fl >> 4) & 7u);
+		}
 		if ((s & 0xff) == 0) { // shrink (reference wf_stripe_shrink, miniwfa.c:144-171) on the interleaved good bits
 			if (tid == 0) sh.red[0] = 0x7fffffff, sh.red[1] = -1;
 			__syncthreads();
@@ -1105,8 +1148,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			if (ghi < 0) { R.status = ST_INTERNAL; return true; }
 			wf_lo = glo, wf_hi = ghi;
 		}
-		cells += hi - lo + 1;
-		if (cells > iter_limit || s > s_limit) { // miniwfa.c:422-425
+		if (kChain) cells -= hi - lo + 1;
+		else cells += hi - lo + 1;
+		if ((kChain ? cells < 0 : cells > iter_limit) || s > s_limit) { // miniwfa.c:422-425
 			R.status = ST_STOPPED;
 			return true;
 		}
@@ -1123,6 +1167,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	for (;;)
 		if (step()) break;
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	if (kChain) cells = (fresh(A).max_iter > 0 ? fresh(A).max_iter : INT64_MAX) - cells;
 	R.s = s, R.cells = est_window ? -(int64_t)est_window : cells; // (a pair handed back early: the window it is expected to need, negated, for the host's choice of the next kernel)
 	return R;
 }
