@@ -10,10 +10,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmwf_hip.so")
 SOURCES = ["mwf_band2.hip", "mwf_band2_tab.hip", "mwf_band2_nib.hip", "mwf_band2_e3.hip", "mwf_band2_e4.hip", "mwf_band2_bi.hip", "mwf_band2_bi_deep.hip", "mwf_kernels.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_sys_deep.hip", "mwf_cigar_ops.hip", "mwf_alphabet.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
-HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
-# sources that include another source: mwf_band2_e3.hip / _e4.hip are mwf_band2.hip again, with only the instantiations for gap extensions of 3 / 4,
-# mwf_band2_bi.hip / _bi_deep.hip with only the 512 x 5 / 512 x 6 copies on biased offsets of every set but (2, 1), mwf_band2_tab.hip with only the table form of the first probe, mwf_band2_nib.hip with only the 4-bit form ("alpha16")
-SOURCE_DEPS = {"mwf_band2_e3.hip": ["mwf_band2.hip"], "mwf_band2_e4.hip": ["mwf_band2.hip"], "mwf_band2_bi.hip": ["mwf_band2.hip"], "mwf_band2_bi_deep.hip": ["mwf_band2.hip"], "mwf_band2_tab.hip": ["mwf_band2.hip"], "mwf_band2_nib.hip": ["mwf_band2.hip"]}
+HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_band2_kernel.h"), os.path.join(CSRC, "mwf_band2_dispatch.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
+# the seven units of the packed band kernel (its template: mwf_band2_kernel.h, which instantiations each holds: mwf_band2_dispatch.h); `python -m miniwfa_amd.build --list-band-units`
+# prints them for the scripts under profiles/ that build a variant of them
+BAND2_UNITS = [s for s in SOURCES if s.startswith("mwf_band2")]
 
 
 def hipcc() -> str:
@@ -47,8 +47,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             continue
         obj = os.path.join(objdir, name + ".o")
         objs.append(obj)
-        src_time = max(os.path.getmtime(os.path.join(CSRC, d)) for d in [name, *SOURCE_DEPS.get(name, [])])
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(src_time, hdr_time):
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_time):
             jobs.append([hipcc(), *flags, "-c", src, "-o", obj])
 
     def run(cmd):
@@ -73,12 +72,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 # which source file defines a kernel (by the start of its symbol): what a counter profile of that kernel is a profile OF
-KERNEL_FILES = {"wfa_band2_kernel": "mwf_band2.hip", "wfa_band2_tab_kernel": "mwf_band2.hip", "wfa_band2_nib_kernel": "mwf_band2.hip", "wfa_sys_kernel": "mwf_sys.hip", "wfa_sys_seg_kernel": "mwf_sys.hip", "wfa_batch_kernel": "mwf_kernels.hip",
-                "wfa_lane_kernel": "mwf_lane.hip", "wfa_mid_kernel": "mwf_mid.hip"}
-# further files that hold a source file's kernel code: the whole-device kernel's template lives in mwf_sys_pass.h and is instantiated by two units — a
+KERNEL_FILES = {"wfa_band2_kernel": "mwf_band2_kernel.h", "wfa_band2_tab_kernel": "mwf_band2_kernel.h", "wfa_band2_nib_kernel": "mwf_band2_kernel.h", "wfa_sys_kernel": "mwf_sys.hip", "wfa_sys_seg_kernel": "mwf_sys.hip",
+                "wfa_batch_kernel": "mwf_kernels.hip", "wfa_lane_kernel": "mwf_lane.hip", "wfa_mid_kernel": "mwf_mid.hip"}
+# further files that hold a kernel's code: the whole-device kernel's template lives in mwf_sys_pass.h and is instantiated by two units — a
 # wfa_sys_kernel<3,1,...> symbol comes from mwf_sys_deep.hip, and the prefix alone does not say which unit, so both are part of the fingerprint
-# ... and the band kernel's for gap extensions of 3 / 4 by mwf_band2_e3.hip / _e4.hip, its copies on biased offsets by mwf_band2_bi.hip / _bi_deep.hip, which include mwf_band2.hip
-KERNEL_HEADERS = {"mwf_sys.hip": ["mwf_sys_pass.h", "mwf_sys_deep.hip"], "mwf_band2.hip": ["mwf_band2_e3.hip", "mwf_band2_e4.hip", "mwf_band2_bi.hip", "mwf_band2_bi_deep.hip", "mwf_band2_tab.hip", "mwf_band2_nib.hip"]}
+# ... and the band kernel's template (mwf_band2_kernel.h) by seven, chosen by mwf_band2_dispatch.h
+KERNEL_HEADERS = {"mwf_sys.hip": ["mwf_sys_pass.h", "mwf_sys_deep.hip"], "mwf_band2_kernel.h": ["mwf_band2_dispatch.h", *BAND2_UNITS]}
 
 
 def kernel_fingerprint(symbol: str) -> str | None:
@@ -118,5 +117,8 @@ def build_cli(force: bool = False) -> str:
 
 
 if __name__ == "__main__":
+    if "--list-band-units" in sys.argv or "--list-sources" in sys.argv:   # (for profiles/build_*variant.sh, build_band2_timeline.sh, asm_band2.sh)
+        print(" ".join(BAND2_UNITS if "--list-band-units" in sys.argv else SOURCES))
+        sys.exit(0)
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_cli(force="--force" in sys.argv))

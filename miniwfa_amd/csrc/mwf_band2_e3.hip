@@ -1,6 +1,29 @@
-// mwf_band2_e3.hip — the packed band kernel (mwf_band2.hip) for gap extensions (3, 1) and (3, 2): the same template with E1 / F1 histories of 3 penalties and
-// an edge table of 4 ages.  A unit of its own so that it compiles beside mwf_band2.hip; it defines launch_band2_e3 and band2_occupancy_e3 and nothing else
-// (mwf_band2.hip: MWF_BAND2_DEEP).  Geometries: 64 ... 512 x 3, 512 x 4 and the 1024 x 5 span geometry on 2-bit copies, 768 x 2 byte-wise, each with and
+// mwf_band2_e3.hip — the packed band kernel (mwf_band2_kernel.h) for gap extensions (3, 1) and (3, 2): the same template with E1 / F1 histories of 3 penalties and
+// an edge table of 4 ages.  A unit of its own so that it compiles beside mwf_band2.hip; it defines launch_band2_e3 and band2_occupancy_e3 and nothing else.
+// Geometries: 64 ... 512 x 3, 512 x 4 and the 1024 x 5 span geometry on 2-bit copies, 768 x 2 byte-wise, each with and
 // without traceback — never folded, no copies on biased offsets.  Registers and scratch: profiles/band_deep/band2_deep_registers.txt.
-#define MWF_BAND2_DEEP 3
-#include "mwf_band2.hip"
+#include "mwf_band2_dispatch.h"
+
+namespace mwf {
+
+namespace {
+struct Unit {
+	using Sets = E3Sets;
+	using BiasedSets = NoSets;
+	static constexpr unsigned geos = kGeoPlain;
+};
+} // namespace
+
+int launch_band2_e3(const BatchArgs &a, int grid, const BandGeom &g, void *stream)
+{
+	if (g.packed == 2) return -1; // (no copies of the 512-thread geometry on biased offsets in this unit: mwf_band2_bi_deep.hip)
+	return band2_unit_launch<Unit>(a, grid, g, stream);
+}
+
+int band2_occupancy_e3(const Penalty &p, const BandGeom &g, bool cigar)
+{
+	if (g.packed == 2) return 0;
+	return band2_unit_occupancy<Unit>(p, g, cigar);
+}
+
+} // namespace mwf

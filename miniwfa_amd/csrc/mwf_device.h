@@ -1,4 +1,4 @@
-// mwf_device.h — device-side helpers shared by every alignment kernel (mwf_kernels.hip generic, mwf_band2.hip packed band,
+// mwf_device.h — device-side helpers shared by every alignment kernel (mwf_kernels.hip generic, mwf_band2_kernel.h packed band,
 // mwf_lane.hip short pairs, mwf_mid.hip mid-size pairs of small batches, mwf_sys.hip whole device): the recurrence and its
 // traceback byte, kernel-argument access, the shared traceback, per-pair memory views and outputs.
 #pragma once
@@ -102,7 +102,7 @@ __device__ __forceinline__ int32_t lds_extend8(const uint8_t *lt, const uint8_t 
 }
 // 2-bit copies (pairs of plain A/C/G/T): sixteen bases per dword, base j at bits 2*(j & 15) of dword j >> 4 — one ds_read2_b32 and one
 // v_alignbit per sequence give SIXTEEN bases from any position: a trip is two LDS instructions instead of six, and a run must be
-// twice as long before a second trip is needed (as in mwf_band2.hip).
+// twice as long before a second trip is needed (as in mwf_band2_kernel.h).
 __device__ __forceinline__ uint32_t lds_seq16(const uint8_t *b2, int32_t j)
 {
 	const uint32_t *p = (const uint32_t*)(b2 + ((j >> 4) << 2));
@@ -270,7 +270,7 @@ struct PairMem {
 	int32_t ep_ow, ep_p, ep_kw;
 	// rows of a fixed width that all start at the same column (mwf_lane.hip): byte of (row, col) at row * tb_stride + col - tb_left; 0: not this layout
 	int32_t tb_stride, tb_left;
-	// Packed band kernel, folded form with traceback (mwf_band2.hip): bits 3 and 4 of a byte look FORWARD — E1 (F1) of this cell exceeds the H it
+	// Packed band kernel, folded form with traceback (mwf_band2_kernel.h): bits 3 and 4 of a byte look FORWARD — E1 (F1) of this cell exceeds the H it
 	// would be opened from, i.e. the E1 (F1) of penalty + e1 in the neighbouring column is an extension of this one — instead of saying whether
 	// this cell's own E1 (F1) was extended: the walk reads them from the cell an extension would come from.
 	int32_t tb_fwd;

@@ -94,7 +94,7 @@ struct BatchArgs {
 	int32_t ring16;            // generic kernel with E2/F2 in LDS: the ring rows in HBM hold 16-bit codes (half the traffic; offsets up to 65532)
 	int32_t scalar_generic;    // generic kernel: 1 = one column per lane (forward_pass) also where the four-columns-per-lane pass applies
 	int32_t band_lds_seq;      // band kernel with the sequences in LDS: bytes of the sequence copy (bookkeeping words and edge table sit behind it)
-	int32_t band_fold;         // packed band kernel, score-only, o1 == x: the folded form (mwf_band2.hip: FOLD) — no loads of the row the first gap piece opens from
+	int32_t band_fold;         // packed band kernel, score-only, o1 == x: the folded form (mwf_band2_kernel.h: FOLD) — no loads of the row the first gap piece opens from
 	int32_t coop_groups, coop_group_size; // pairs side by side on the whole-device kernel and workgroups per pair (grid = product)
 	int64_t coop_edge_stride;  // ints between two groups' granule arrays
 	int64_t coop_sedge_off;    // ints from a group's granule array to its array of provenance granules (true low-memory first pass)
@@ -187,10 +187,10 @@ int launch_alphabet(const AlphabetArgs &a, int block, void *stream);
 int  bigring_kernel_occupancy();                     // ... of the big-ring form (penalty sets with max(x, o1+e1, o2+e2) >= 256)
 int  batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ring16);   // resident workgroups per CU for that block size
 
-// geometry of a launch of the band family (mwf_band2.hip packed band kernel, mwf_lane.hip, mwf_mid.hip)
+// geometry of a launch of the band family (mwf_band2_kernel.h packed band kernel, mwf_lane.hip, mwf_mid.hip)
 struct BandGeom {
 	int block;        // threads per workgroup: 256 (x2 chunks), 768 (x2 chunks) or 512 (x3 chunks, packed state)
-	int packed;       // 1: the packed band kernel (mwf_band2.hip: E/F register state as int16 pairs, 16-bit H rows); 2: its 512-thread geometry's five / six-slot copies on biased offsets
+	int packed;       // 1: the packed band kernel (mwf_band2_kernel.h: E/F register state as int16 pairs, 16-bit H rows); 2: its 512-thread geometry's five / six-slot copies on biased offsets
 	int span;         // columns the workgroup can hold: waves * chunks * 256 (balanced kernel: columns of its LDS state ring)
 	int lds_bytes;    // dynamic LDS for the sequence copy (0: read sequences from global memory)
 	int seq2;         // packed kernel: the sequence copy holds 2 bits per base (pairs of plain A/C/G/T; others come back as ST_ALPHABET)
@@ -234,6 +234,20 @@ int  launch_mid(const BatchArgs &a, int grid, int block, int lds, bool seq2, voi
 bool band2_supported(const Penalty &p);
 int  launch_band2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar);
+// ... which route to the units that hold the other instantiations (mwf_band2_dispatch.h; -1 / 0: the unit does not hold that launch, -2: the launch failed):
+// gap extensions of 3 and 4, the 512-thread geometry's copies on biased offsets of every set but (2,1), the table form, the 4-bit form
+int  launch_band2_e3(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_e4(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_bi1(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_bi2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_tab(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_nib(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  band2_occupancy_e3(const Penalty &p, const BandGeom &g, bool cigar);
+int  band2_occupancy_e4(const Penalty &p, const BandGeom &g, bool cigar);
+int  band2_occupancy_bi1(const Penalty &p, const BandGeom &g, bool cigar);
+int  band2_occupancy_bi2(const Penalty &p, const BandGeom &g, bool cigar);
+int  band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar);
+int  band2_occupancy_nib(const Penalty &p, const BandGeom &g, bool cigar);
 bool band2_nib_supported(const Penalty &p);          // the 4-bit form (mwf_band2_nib.hip, BandGeom::nib) has kernels for these penalties: gap extensions (2,1)
 bool band2_tab_supported(const Penalty &p, bool band_fold); // the table form of the first probe (mwf_band2_tab.hip, BandGeom::tab) has kernels for these penalties
 bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for the set: every set band2_supported takes

@@ -1,7 +1,7 @@
 // mwf_lane.hip — one wave per pair, one diagonal per lane, everything on chip: the kernel for SHORT pairs (single calls of
 // mwf_wfa_exact on a read-sized pair, batches of short reads).
 //
-// A 200 bp pair at 5 % divergence ends near penalty 36 with a window of ~45 diagonals.  The packed band kernel (mwf_band2.hip)
+// A 200 bp pair at 5 % divergence ends near penalty 36 with a window of ~45 diagonals.  The packed band kernel (mwf_band2_kernel.h)
 // computes a 256-column chunk for it per penalty — ~800 instructions of a lone wave, 1.7 us — and keeps its H rows in HBM.  Here a
 // lane owns ONE column per 64-column chunk (column = diagonal + tl + 1, as everywhere), so a penalty is the recurrence on one cell
 // plus its match extension, once per chunk the window has reached:
@@ -42,7 +42,7 @@ constexpr int32_t kDead16 = -32768;
 
 __device__ __forceinline__ int32_t row_ints(int nc) { return 32 * nc + 2; } // a row: pad, 64 x nc columns, pad as int16, rounded up to dwords
 
-// FOLD (score-only, o1 == x as in the default penalties; the packed band kernel's form, mwf_band2.hip): the E1 / F1 rows hold
+// FOLD (score-only, o1 == x as in the default penalties; the packed band kernel's form, mwf_band2_kernel.h): the E1 / F1 rows hold
 // max(E1, H[s-x]) / max(F1, H[s-x]) — what the reference computes e1 penalties later from the row of lag o1+e1 (miniwfa.c:267-278) — and that
 // row is not read: two LDS reads less per chunk.  Windows never shrink here (the kernel hands a pair back before the first shrink), so a
 // column that held a live H was computed at every later penalty.

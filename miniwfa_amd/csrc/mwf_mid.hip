@@ -1,7 +1,7 @@
 // mwf_mid.hip — one workgroup per pair, one diagonal per lane, every wavefront ring in LDS: the kernel for a FEW mid-size pairs
 // (a single mwf_wfa_exact call on a pair of a few thousand bases — the reference's own usage, main.c:67-72 — or a handful of them).
 //
-// Between the lane kernel (mwf_lane.hip: one wave per pair, pairs of up to 400 bases) and the packed band kernel (mwf_band2.hip: a
+// Between the lane kernel (mwf_lane.hip: one wave per pair, pairs of up to 400 bases) and the packed band kernel (mwf_band2_kernel.h: a
 // wave computes a 256-column chunk per penalty, H rows in HBM) a lone 2 kb pair cost 1.9 us per penalty: ~800 instructions of one or
 // two waves plus the HBM round trip of the rows, whatever the window.  Here the lane kernel's design is spread over the waves of a
 // workgroup:
@@ -80,7 +80,7 @@ __host__ __device__ inline MidLayout mid_layout(int32_t nH, int32_t e1, int32_t 
 	return L;
 }
 
-// FOLD (score-only, o1 == x; the packed band kernel's form, mwf_band2.hip): the E1 / F1 rows hold max(E1, H[s-x]) / max(F1, H[s-x]) and the
+// FOLD (score-only, o1 == x; the packed band kernel's form, mwf_band2_kernel.h): the E1 / F1 rows hold max(E1, H[s-x]) / max(F1, H[s-x]) and the
 // row of lag o1+e1 is not read — two LDS reads less per group.  Every penalty writes the window and nH columns either side, and a window moves
 // by one column per penalty (a shrink only cuts it): the columns next to the window of penalty s were written at penalty s - e1.
 template <int T, bool TB, bool S2, bool FOLD, typename ArgsT>

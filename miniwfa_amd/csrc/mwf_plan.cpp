@@ -45,7 +45,7 @@ constexpr int64_t kBandWideWindow = (8 * 3 - 1) * 256 - 64;
 // three slots on windows those hold (1024 x 10 kb @ 5 %: 17.7 against 17.4 ms) — and 17.7 against 24.8 ms on a batch in which ONE pair outgrows them
 // late and is re-run alone (three of four seeds of that batch shape, profiles/r04/wide4.txt).  Taken when a forecast or the batch's last align says so.
 constexpr int64_t kBandWide4Window = (8 * 4 - 1) * 256 - 64;
-// ... and the 1024-thread span geometry (16 waves x kBand2SpanK chunks, offsets biased by the target length: mwf_band2.hip wide_bias)
+// ... and the 1024-thread span geometry (16 waves x kBand2SpanK chunks, offsets biased by the target length: mwf_band2_kernel.h wide_bias)
 constexpr int64_t kBandSpanMaxSeq = 62000;
 inline int64_t band_span_window() { return ((int64_t)band2_span_chunks() - 1) * 256 - 64; }
 

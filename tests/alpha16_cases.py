@@ -3,6 +3,8 @@ Python, the batches the GPU tests align and the edge cases of the 4-bit band ker
 trips of eight bases, whole-wave trips of 512).  Nothing here needs a device; expected answers always come from the oracle on the ORIGINAL bytes."""
 from __future__ import annotations
 
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -316,25 +318,11 @@ def expected(orc, key: str, pairs, flag: int = 1, **pen):
     return _expected[k]
 
 
+NIB_OBJ = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_nib.hip.o")
+
+
 def nib_object_kernels():
-    """The demangled wfa_band2_nib_kernel<...> argument lists in mwf_band2_nib.hip.o (band_matrix.Inst), and every other kernel symbol of that object."""
-    import os
-    import re
-    import shutil
-    import subprocess
-    obj = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_nib.hip.o")
-    assert os.path.exists(obj), "no " + os.path.relpath(obj, bm.ROOT) + " (the library was not built from this tree)"
-    readelf = next((p for p in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf"), shutil.which("llvm-readelf") or "") if p and os.path.exists(p)), None)
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    assert readelf and cxxfilt, "llvm-readelf or c++filt not found"
-    syms = subprocess.run([readelf, "-sW", obj], check=True, capture_output=True, text=True).stdout
-    dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
-    nib = set()
-    for m in re.finditer(r"wfa_band2_nib_kernel<([^<>]*)>", dem):
-        vals = []
-        for a in m.group(1).split(","):
-            a = re.sub(r"^\(\w+\)", "", a.strip()).strip("()")
-            vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a))
-        nib.add(bm.Inst(*vals))
-    others = set(re.findall(r"\b(wfa_\w+_kernel)<", dem)) - {"wfa_band2_nib_kernel"}
-    return nib, others
+    """The wfa_band2_nib_kernel<...> instantiations in mwf_band2_nib.hip.o's gfx950 code object (band_matrix.Inst), and every other kernel of that object."""
+    got = bm.device_kernels(NIB_OBJ, "wfa_band2_nib_kernel")
+    assert not isinstance(got, str), got
+    return set(got[0]), {re.search(r"(\w+)<", name).group(1) for name in got[1]}

@@ -110,42 +110,10 @@ def object_instantiations(unit: str):
 
 
 def device_instantiations(unit: str):
-    """{Inst} of the KERNELS in the unit's gfx950 code object — what is compiled for the GPU, launchable or not — or a string saying why it cannot be read
-    here (band_deep_matrix.device_instantiations, on this module's objects)."""
-    return _device_instantiations(BIASED_OBJS[unit])
-
-
-def _device_instantiations(obj: str):
-    import re
-    import shutil
-    import subprocess
-    import tempfile
-    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-    tools = {t: (os.path.join(llvm, t) if os.path.exists(os.path.join(llvm, t)) else shutil.which(t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    if not all(tools.values()) or not cxxfilt:
-        return "llvm-objcopy, clang-offload-bundler, llvm-readelf or c++filt not found"
-    if not os.path.exists(obj):
-        return "no " + os.path.basename(obj) + " (the library was not built from this tree)"
-    with tempfile.TemporaryDirectory() as d:
-        fb, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
-        subprocess.run([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(d, "copy.o")], check=True, capture_output=True)
-        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fb, "--output=" + co],
-                       check=True, capture_output=True)
-        syms = subprocess.run([tools["llvm-readelf"], "-sW", co], check=True, capture_output=True, text=True).stdout
-    dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
-    out = set()
-    for ln in dem.splitlines():
-        m = re.search(r"\bFUNC\b.*wfa_band2_kernel<([^<>]*)>", ln)
-        if not m:
-            continue
-        vals = []
-        for a in m.group(1).split(","):
-            a = re.sub(r"^\(\w+\)", "", a.strip()).strip("()")
-            vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a))
-        assert len(vals) == 8, ln
-        out.add(Inst(*vals))
-    return out
+    """{Inst} of the KERNELS in the unit's gfx950 code object — what is compiled for the GPU, launchable or not (band_matrix.device_kernels) — or a string
+    saying why it cannot be read here."""
+    got = base.device_kernels(BIASED_OBJS[unit], "wfa_band2_kernel")
+    return got if isinstance(got, str) else set(got[0])
 
 
 def tunables(g: Geom, band_fold: int):

@@ -1,4 +1,4 @@
-"""Inputs of the tests of the table form's chunk chain (miniwfa_amd/csrc/mwf_band2.hip, kChain / kGeo: a slot's probe geometry — the room bounds rj and the
+"""Inputs of the tests of the table form's chunk chain (miniwfa_amd/csrc/mwf_band2_kernel.h, kChain / kGeo: a slot's probe geometry — the room bounds rj and the
 query's table index of the lane's columns — is computed where the slot's chunk is assigned, remap(), and read from registers for as long as the slot keeps the
 chunk; the rare tests of a chunk are laid out behind its straight line).  Built on the CPU from the oracle's CIGAR and band trace:
 
@@ -256,33 +256,7 @@ def traces(orc, name: str):
 
 
 def table_kernel_notes():
-    """{demangled kernel name: {field: int}} of the kernels of mwf_band2_tab.hip.o, from the metadata notes of its gfx950 code object."""
-    import os
-    import re
-    import shutil
-    import subprocess
-    import tempfile
-    obj = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_tab.hip.o")
-    assert os.path.exists(obj), "no " + os.path.relpath(obj, bm.ROOT) + " (the library was not built from this tree)"
-    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-    tools = {t: (os.path.join(llvm, t) if os.path.exists(os.path.join(llvm, t)) else shutil.which(t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    assert all(tools.values()) and cxxfilt, "llvm-objcopy, clang-offload-bundler, llvm-readelf or c++filt not found"
-    with tempfile.TemporaryDirectory() as d:
-        fb, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
-        subprocess.run([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(d, "copy.o")], check=True, capture_output=True)
-        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fb, "--output=" + co],
-                       check=True, capture_output=True)
-        notes = subprocess.run([tools["llvm-readelf"], "--notes", co], check=True, capture_output=True, text=True).stdout
-    out, cur = {}, {}
-    for ln in notes.splitlines():   # (a kernel's fields come in alphabetical order and end with .symbol ... .wavefront_size)
-        m = re.match(r"\s*(?:- )?\.(\w+):\s*(\S+)\s*$", ln)
-        if not m:
-            continue
-        k, v = m.groups()
-        if k in ("private_segment_fixed_size", "sgpr_spill_count"):   # (both in front of .symbol)
-            cur[k] = int(v)
-        elif k == "symbol":
-            out[subprocess.run([cxxfilt, v[:-3] if v.endswith(".kd") else v], check=True, capture_output=True, text=True).stdout.strip()] = cur
-            cur = {}
-    return out
+    """{demangled kernel name: {field: int}} of the kernels of mwf_band2_tab.hip.o, from the metadata notes of its gfx950 code object (band_matrix.device_kernels)."""
+    got = bm.device_kernels(tc.TAB_OBJ, "wfa_band2_tab_kernel")
+    assert not isinstance(got, str), got
+    return {v["name"]: v for part in got for v in part.values()}

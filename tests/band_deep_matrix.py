@@ -80,40 +80,10 @@ def object_instantiations(e1: int):
 
 
 def device_instantiations(e1: int):
-    """{Inst} of the KERNELS in the unit's gfx950 code object — what is compiled for the GPU, launchable or not — or a string saying why it cannot be read
-    here.  object_instantiations reads the host symbol table, i.e. the kernel stubs: a dispatch arm that can never run leaves no stub behind but still
-    instantiates its kernels on the device side.  The code object is the gfx950 entry of the object's .hip_fatbin section (llvm-objcopy, clang-offload-bundler)."""
-    import re
-    import shutil
-    import subprocess
-    import tempfile
-    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-    tools = {t: (os.path.join(llvm, t) if os.path.exists(os.path.join(llvm, t)) else shutil.which(t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    if not all(tools.values()) or not cxxfilt:
-        return "llvm-objcopy, clang-offload-bundler, llvm-readelf or c++filt not found"
-    obj = DEEP_OBJS[e1]
-    if not os.path.exists(obj):
-        return "no " + os.path.basename(obj) + " (the library was not built from this tree)"
-    with tempfile.TemporaryDirectory() as d:
-        fb, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
-        subprocess.run([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(d, "copy.o")], check=True, capture_output=True)
-        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fb, "--output=" + co],
-                       check=True, capture_output=True)
-        syms = subprocess.run([tools["llvm-readelf"], "-sW", co], check=True, capture_output=True, text=True).stdout
-    dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
-    out = set()
-    for ln in dem.splitlines():
-        m = re.search(r"\bFUNC\b.*wfa_band2_kernel<([^<>]*)>", ln)
-        if not m:
-            continue
-        vals = []
-        for a in m.group(1).split(","):
-            a = re.sub(r"^\(\w+\)", "", a.strip()).strip("()")
-            vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a))
-        assert len(vals) == 8, ln
-        out.add(Inst(*vals))
-    return out
+    """{Inst} of the KERNELS in the unit's gfx950 code object — what is compiled for the GPU, launchable or not (band_matrix.device_kernels) — or a string
+    saying why it cannot be read here."""
+    got = base.device_kernels(DEEP_OBJS[e1], "wfa_band2_kernel")
+    return got if isinstance(got, str) else set(got[0])
 
 
 def tunables(g: Geom):

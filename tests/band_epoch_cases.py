@@ -1,4 +1,4 @@
-"""Inputs of the window-epoch tests of the packed band kernel (miniwfa_amd/csrc/mwf_band2.hip: a penalty whose window meets the same chunks as the last one
+"""Inputs of the window-epoch tests of the packed band kernel (miniwfa_amd/csrc/mwf_band2_kernel.h: a penalty whose window meets the same chunks as the last one
 reuses the slot state the last full header derived).  Every case is a batch of small pairs chosen ON THE CPU, from the oracle's band trace alone, for the one
 moment at which a stale cache would show, and names the penalty at which it happens:
 

@@ -1,4 +1,4 @@
-"""The instantiations of the packed band kernel (miniwfa_amd/csrc/mwf_band2.hip, wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), one
+"""The instantiations of the packed band kernel (miniwfa_amd/csrc/mwf_band2_kernel.h, wfa_band2_kernel<T, K, E1, E2, TB, S2, BI4, FOLD>), one
 entry each, with what reaches it — tunables, penalty sets, inputs — and the inputs of its two test groups, sized on the CPU from the oracle alone.
 
   tests/test_band_matrix_cpu.py   the set of entries EQUALS the set of instantiations in the built object; the inputs of every cell hold what
@@ -11,11 +11,11 @@ Rule: an instantiation is added (or removed, or re-parameterised) together with 
 fit = the pair's widest window (Oracle.band_trace) is at most the geometry's admission window AND the rules below, each of which restates
 a documented hand-back of the kernel in terms of the oracle's band trace and the pair's lengths — never of what the device did:
   chunks    the kernel holds whole 256-column chunks, NWK - 1 of them counted from the chunk its slot mapping starts at, and the mapping follows
-            a window whose start moves up only kAgeOut penalties late (mwf_band2.hip: the test in front of `gl_next`, and the remap after a penalty)
+            a window whose start moves up only kAgeOut penalties late (mwf_band2_kernel.h: the test in front of `gl_next`, and the remap after a penalty)
   forecast  the 64-, 128- and 256-thread geometries (at penalties 64, 256, 1024) and the span geometry (1024, 4096) hand a pair back EARLY when its
             progress so far says its window will outgrow them (mwf_device.h window_forecast; the furthest offset comes from Oracle.band_trace_far).
             A pair within 5 % of that threshold counts as not fit: the device's furthest offset is taken over the chunks it computes
-  range     biased offsets (span geometry, 512 x 5 / 512 x 6): checked every 256 penalties (mwf_band2.hip wide_bias, kBiasMargin), and the
+  range     biased offsets (span geometry, 512 x 5 / 512 x 6): checked every 256 penalties (mwf_band2_kernel.h wide_bias, kBiasMargin), and the
             window's start must stay within 65 535 columns of the last column
 Of the candidates that pass the plain width test, the share the rules drop is reported per cell and bounded (MAX_DROPPED_SHARE)."""
 from __future__ import annotations
@@ -30,7 +30,7 @@ from miniwfa_amd.synth import synth_pair
 from oracle.pyoracle import make_opt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAND2_SRC = os.path.join(ROOT, "miniwfa_amd", "csrc", "mwf_band2.hip")
+BAND2_SRC = os.path.join(ROOT, "miniwfa_amd", "csrc", "mwf_band2.hip")   # (its checked statement of the template's constants: namespace band2_text)
 BAND2_OBJ = os.path.join(ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2.hip.o")
 ORACLE_THREADS = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4))
 MAX_DROPPED_SHARE = 0.25
@@ -172,29 +172,86 @@ for _c in ALL_CELLS:   # a run's penalties and band_fold force the entry's E1, E
 
 
 # ---- the instantiations of the built object ---------------------------------------------------------------------------------------------
+def _inst_of(template_args: str) -> Inst:
+    """Inst of a demangled argument list: "512, 3, 2, 1, false, true, false, true" (or with casts: "(bool)1")."""
+    vals = []
+    for a in template_args.split(","):
+        a = re.sub(r"^\(\w+\)", "", a.strip()).strip("()")
+        vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a))
+    assert len(vals) == 8, template_args
+    return Inst(*vals)
+
+
+def _tools(*names):
+    """{tool: path} of LLVM tools (ROCm's, else the PATH's) and c++filt; a missing one maps to None."""
+    import shutil
+    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+    tools = {t: (os.path.join(llvm, t) if os.path.exists(os.path.join(llvm, t)) else shutil.which(t)) for t in names}
+    tools["c++filt"] = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    return tools
+
+
 def object_instantiations(obj: str = BAND2_OBJ):
     """{Inst} parsed from the object's symbol table (llvm-readelf -sW | c++filt), or a string saying why that cannot be done here."""
-    import shutil
     import subprocess
-    readelf = next((p for p in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf"), shutil.which("llvm-readelf") or "") if p and os.path.exists(p)), None)
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    if not readelf or not cxxfilt:
+    tools = _tools("llvm-readelf")
+    if not all(tools.values()):
         return "llvm-readelf or c++filt not found"
     if not os.path.exists(obj):
         return "no " + os.path.relpath(obj, ROOT) + " (the library was not built from this tree)"
-    syms = subprocess.run([readelf, "-sW", obj], check=True, capture_output=True, text=True).stdout
-    dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
-    out = set()
-    for m in re.finditer(r"wfa_band2_kernel<([^<>]*)>", dem):
-        args = [a.strip() for a in m.group(1).split(",")]
-        assert len(args) == 8, m.group(0)
-        vals = []
-        for a in args:
-            a = re.sub(r"^\(\w+\)", "", a).strip("()")
-            vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a) if re.fullmatch(r"-?\d+", a) else None)
-        assert None not in vals, m.group(0)
-        out.add(Inst(*vals))
-    return out
+    syms = subprocess.run([tools["llvm-readelf"], "-sW", obj], check=True, capture_output=True, text=True).stdout
+    dem = subprocess.run([tools["c++filt"]], input=syms, check=True, capture_output=True, text=True).stdout
+    return {_inst_of(m.group(1)) for m in re.finditer(r"wfa_band2_kernel<([^<>]*)>", dem)}
+
+
+NOTE_FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def device_kernels(obj: str, kernel: str = "wfa_band2_kernel"):
+    """The KERNELS in the object's gfx950 code object — what is compiled for the GPU, launchable or not: ({Inst: notes} of `kernel`'s instantiations, {demangled
+    name: notes} of every other kernel), or a string saying why the object cannot be read here.  notes: the NOTE_FIELDS of the kernel's metadata note as ints, and
+    "name", its demangled name.  object_instantiations reads the host symbol table, i.e. the kernel stubs: a dispatch arm that can never run leaves no stub
+    behind but still instantiates its kernels on the device side.  The code object is the gfx950 entry of the object's .hip_fatbin section (llvm-objcopy,
+    clang-offload-bundler); its kernels are the entries of its metadata notes (llvm-readelf --notes)."""
+    import subprocess
+    import tempfile
+    tools = _tools("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")
+    if not all(tools.values()):
+        return "llvm-objcopy, clang-offload-bundler, llvm-readelf or c++filt not found"
+    if not os.path.exists(obj):
+        return "no " + os.path.relpath(obj, ROOT) + " (the library was not built from this tree)"
+    with tempfile.TemporaryDirectory() as d:
+        fb, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
+        subprocess.run([tools["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(d, "copy.o")], check=True, capture_output=True)
+        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fb, "--output=" + co],
+                       check=True, capture_output=True)
+        notes = subprocess.run([tools["llvm-readelf"], "--notes", co], check=True, capture_output=True, text=True).stdout
+    kernels, cur = [], None
+    for ln in notes.splitlines():   # (an entry of a list starts with "- "; a kernel's is the one that holds .symbol — its .args entries in front of it hold none of the fields)
+        m = re.match(r"\s*(- )?\.(\w+):\s*(\S+)?\s*$", ln)
+        if not m:
+            continue
+        if m.group(1):
+            cur = {}
+        if cur is None:
+            continue
+        if m.group(2) in NOTE_FIELDS:
+            cur[m.group(2)] = int(m.group(3))
+        elif m.group(2) == "symbol":
+            cur["symbol"] = m.group(3)[:-3] if m.group(3).endswith(".kd") else m.group(3)
+            kernels.append(cur)
+    names = subprocess.run([tools["c++filt"]], input="\n".join(k.pop("symbol") for k in kernels), check=True, capture_output=True, text=True).stdout.split("\n")
+    insts, others = {}, {}
+    for k, name in zip(kernels, names):
+        assert set(k) == set(NOTE_FIELDS), (name, k)
+        k["name"] = name.strip()
+        m = re.search(r"\b" + kernel + r"<([^<>]*)>", name)
+        if m:
+            insts[_inst_of(m.group(1))] = k
+        else:
+            others[k["name"]] = k
+    assert len(insts) + len(others) == len(kernels), "a kernel is listed twice"
+    return insts, others
 
 
 # ---- the host's rules, restated ---------------------------------------------------------------------------------------------------------

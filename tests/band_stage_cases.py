@@ -1,4 +1,4 @@
-"""Inputs of the tests of the table form's every-penalty tail (miniwfa_amd/csrc/mwf_band2.hip, kChain / kLeanTail: the iteration budget is counted DOWN and the
+"""Inputs of the tests of the table form's every-penalty tail (miniwfa_amd/csrc/mwf_band2_kernel.h, kChain / kLeanTail: the iteration budget is counted DOWN and the
 stop test is its sign; a slot's bit in `est` says that its chunk holds column ql + 1, the only column the end cell can lie in, and only such a chunk compares the
 column with the window; the flag word gets a window edge's bits and the end cell's where they arise).  Built on the CPU from the oracle's band trace:
 

@@ -12,6 +12,8 @@ per sequence and column from per-position 8-mer tables; a run of FULL = 8 or mor
 tests/test_band_tab_cpu.py asserts what every case is chosen for; tests/test_band_tab_gpu.py runs them."""
 from __future__ import annotations
 
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -21,7 +23,7 @@ from oracle.pyoracle import make_opt
 import band_matrix as bm
 
 DEFAULT = bm.PEN["default"]
-FULL, FULL_PLAIN, LANE_TRIPS = 8, 16, 4           # mwf_band2.hip: FULL of the table form and of the plain 2-bit probe; per-lane trips of sixteen bases
+FULL, FULL_PLAIN, LANE_TRIPS = 8, 16, 4           # mwf_band2_kernel.h: FULL of the table form and of the plain 2-bit probe; per-lane trips of sixteen bases
 WAVE_WALK_FROM = FULL + 16 * LANE_TRIPS            # a run longer than this is finished by the whole wave
 RUNS = (6, 7, 8, 9, 10, 15, 16, 17, 24, 73)
 ENDS = ("target", "query", "both")
@@ -212,25 +214,11 @@ def lands(g, lohi: np.ndarray, tl: int, d: int, s: int):
     return chunk, rel % nw, rel // nw, (c & 255) >> 2, c & 3
 
 
+TAB_OBJ = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_tab.hip.o")
+
+
 def tab_object_kernels():
-    """The demangled wfa_band2_tab_kernel<...> argument lists in mwf_band2_tab.hip.o, and every other kernel symbol of that object."""
-    import os
-    import re
-    import shutil
-    import subprocess
-    obj = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_tab.hip.o")
-    assert os.path.exists(obj), "no " + os.path.relpath(obj, bm.ROOT) + " (the library was not built from this tree)"
-    readelf = next((p for p in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf"), shutil.which("llvm-readelf") or "") if p and os.path.exists(p)), None)
-    cxxfilt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
-    assert readelf and cxxfilt, "llvm-readelf or c++filt not found"
-    syms = subprocess.run([readelf, "-sW", obj], check=True, capture_output=True, text=True).stdout
-    dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
-    tab = set()
-    for m in re.finditer(r"wfa_band2_tab_kernel<([^<>]*)>", dem):
-        vals = []
-        for a in m.group(1).split(","):
-            a = re.sub(r"^\(\w+\)", "", a.strip()).strip("()")
-            vals.append({"true": 1, "false": 0}[a] if a in ("true", "false") else int(a))
-        tab.add(bm.Inst(*vals))
-    others = set(re.findall(r"\b(wfa_\w+_kernel)<", dem)) - {"wfa_band2_tab_kernel"}
-    return tab, others
+    """The wfa_band2_tab_kernel<...> instantiations in mwf_band2_tab.hip.o's gfx950 code object (band_matrix.Inst), and every other kernel of that object."""
+    got = bm.device_kernels(TAB_OBJ, "wfa_band2_tab_kernel")
+    assert not isinstance(got, str), got
+    return set(got[0]), {re.search(r"(\w+)<", name).group(1) for name in got[1]}

@@ -79,7 +79,7 @@ def check_retries(got, bound, label, bad, log):
 # ---- profiles/fuzz_fold.py: folded against unfolded form of the packed band kernel, and both against the oracle -------------------------
 def fuzz_fold(seed=1, n=400, log=False, long_sets=True, penalty_sets=None):
     """Shapes that move the window's start up (length-skewed and unrelated pairs, long gaps), fuzz pairs, 10-20 kb pairs; penalty sets
-    with o1 == x (the fold's condition, mwf_band2.hip FOLD; reference recurrence miniwfa.c:267-278)."""
+    with o1 == x (the fold's condition, mwf_band2_kernel.h FOLD; reference recurrence miniwfa.c:267-278)."""
     orc = Oracle()
     sets = {
         "skewed 200-3000": skewed_pairs(seed, n, 200, 3000),

@@ -104,7 +104,7 @@ def test_default_routing_10kb_batch(oracle, tag, capfd, monkeypatch):
 @pytest.mark.parametrize("tag", sorted(PEN))
 def test_identical_and_near_identical_pairs(oracle, tag, capfd, monkeypatch):
     """0 % and 1 % divergence at 12 - 14 kb: offsets run to the target's end within a few penalties while everything else is dead — the values the range checks
-    of the biased form look at (mwf_band2.hip wide_bias).  The copies finish every pair; the 12 kb reference vector rides along."""
+    of the biased form look at (mwf_band2_kernel.h wide_bias).  The copies finish every pair; the 12 kb reference vector rides along."""
     from miniwfa_amd.synth import synth_pair
     monkeypatch.setenv("MWF_DEBUG", "1")
     p = PEN[tag]

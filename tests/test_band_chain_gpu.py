@@ -1,4 +1,4 @@
-"""The table form's chunk chain (mwf_band2.hip, kChain / kGeo: per-slot probe geometry in registers, the interior chunk as a straight line) on the inputs of
+"""The table form's chunk chain (mwf_band2_kernel.h, kChain / kGeo: per-slot probe geometry in registers, the interior chunk as a straight line) on the inputs of
 tests/band_chain_cases.py, whose properties tests/test_band_chain_cpu.py asserts.  Geometry forced to 512 threads on three and on four chunk slots, score-only and
 with CIGAR, "probe_table" 1: s, n_iter and the CIGAR words equal the oracle's and, bit for bit, those of the same align with "probe_table" 0 (the plain form
 recomputes the geometry every penalty); one launch, no pair handed back, and the launch record names the table form."""

@@ -1,4 +1,4 @@
-"""The packed band kernel's window epoch (mwf_band2.hip: a penalty whose window meets the same chunks as the last one reuses the slot state of the last full
+"""The packed band kernel's window epoch (mwf_band2_kernel.h: a penalty whose window meets the same chunks as the last one reuses the slot state of the last full
 header) on the inputs at which a stale cache would show — tests/band_epoch_cases.py, whose properties tests/test_band_epoch_cpu.py asserts.  s, n_iter and
 the CIGAR words equal the oracle's; the launch record names the geometry the case was built for."""
 import re

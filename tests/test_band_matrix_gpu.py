@@ -9,7 +9,7 @@ Per cell and run (penalty set, band_fold), two aligns on a fresh engine:
 Score-only cells also equal what their CIGAR twin computed on the same inputs.  Integer work: no tolerance anywhere.
 
 That the cells can fail was tried once with a library built from a copy of the sources in which one computed value was changed — the upper threshold of the
-biased copies' range check (mwf_band2.hip `top`) lowered to 8000, so that the check fires early: the eight cells of 512 x 5 / 512 x 6 on biased offsets went red by
+biased copies' range check (mwf_band2_kernel.h `top`) lowered to 8000, so that the check fires early: the eight cells of 512 x 5 / 512 x 6 on biased offsets went red by
 "fit pairs were handed back" (n_retries 16 and 18 for 16 fit pairs, the launch record showing the span geometry and then the generic kernel taking them); the four
 512 x 4 (2,1) cells run beside them as a control went red too, in their overflow group, whose re-run goes through the span geometry — biased offsets as well — and
 came back as an error of the library ("still unfinished after every retry").  Nothing faulted."""

@@ -1,12 +1,6 @@
 """Every case of the tests of the table form's every-penalty tail (tests/band_stage_cases.py) does what it is chosen for, by the oracle's band trace alone: where the
 iteration budget runs out, which slot's chunk holds the end column at the pair's last penalty, for how long that chunk runs before the window reaches the column;
 and the four table kernels still use no scratch and at most 128 VGPRs."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import band_matrix as bm
 import band_chain_cases as cc
 import band_stage_cases as sc
@@ -61,19 +55,12 @@ def test_which_pairs_run_on_three_slots(oracle):
 
 
 def test_table_kernels_registers():
-    obj = os.path.join(bm.ROOT, "miniwfa_amd", "csrc", "build", "mwf_band2_tab.hip.o")
-    assert os.path.exists(obj), "no " + os.path.relpath(obj, bm.ROOT) + " (the library was not built from this tree)"
-    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-    tool = {t: (os.path.join(llvm, t) if os.path.exists(os.path.join(llvm, t)) else shutil.which(t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    assert all(tool.values()), tool
-    with tempfile.TemporaryDirectory() as d:
-        fb, co = os.path.join(d, "fatbin"), os.path.join(d, "gfx950.co")
-        subprocess.run([tool["llvm-objcopy"], "--dump-section", ".hip_fatbin=" + fb, obj, os.path.join(d, "copy.o")], check=True, capture_output=True)
-        subprocess.run([tool["clang-offload-bundler"], "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fb, "--output=" + co],
-                       check=True, capture_output=True)
-        notes = subprocess.run([tool["llvm-readelf"], "--notes", co], check=True, capture_output=True, text=True).stdout
-    scratch = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", notes)]
-    vgprs = [int(x) for x in re.findall(r"\.vgpr_count:\s*(\d+)", notes)]
-    spilled = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s*(\d+)", notes)]
+    import band_tab_cases as tc
+    got = bm.device_kernels(tc.TAB_OBJ, "wfa_band2_tab_kernel")
+    assert not isinstance(got, str), got
+    notes = list(got[0].values()) + list(got[1].values())
+    scratch = [k["private_segment_fixed_size"] for k in notes]
+    vgprs = [k["vgpr_count"] for k in notes]
+    spilled = [k["vgpr_spill_count"] for k in notes]
     assert len(scratch) == len(vgprs) == len(spilled) == 4, (scratch, vgprs, spilled)
     assert scratch == [0] * 4 and spilled == [0] * 4 and max(vgprs) <= 128, (scratch, vgprs, spilled)

@@ -1,4 +1,4 @@
-"""The table form's every-penalty tail (mwf_band2.hip, kChain / kLeanTail: the iteration budget counted down, the end column's chunk marked in `est`, the flag word
+"""The table form's every-penalty tail (mwf_band2_kernel.h, kChain / kLeanTail: the iteration budget counted down, the end column's chunk marked in `est`, the flag word
 written where its bits arise, read early behind the barrier) on the inputs of tests/band_stage_cases.py, whose properties tests/test_band_stage_cpu.py asserts.
 Geometry forced to 512 threads on three and on four chunk slots, score-only and with CIGAR: s, n_iter and the CIGAR words equal the oracle's and, bit for bit,
 those of the same align with "probe_table" 0 (the plain form keeps the counter and the three compares); one launch, no pair handed back."""

@@ -771,7 +771,7 @@ def test_window_start_climbing_under_default_routing(oracle):
 
 def test_folded_band_kernel_against_unfolded_and_oracle(oracle):
     """Score-only with o1 == x (the default penalties) the packed band kernel keeps max(E1, H[s-x]) in the registers that held E1 and never loads
-    the row of lag o1+e1 (mwf_band2.hip: FOLD).  Pairs whose window moves UP (a query much shorter or longer than its target: diagonals run out
+    the row of lag o1+e1 (mwf_band2_kernel.h: FOLD).  Pairs whose window moves UP (a query much shorter or longer than its target: diagonals run out
     of the matrix and the window's start climbs across chunk boundaries — the slot mapping must follow late), shrinks, several penalty sets
     with o1 == x and one without: folded == unfolded == oracle (s, n_iter), and the folded form's CIGARs == the oracle's."""
     rng = np.random.default_rng(4242)
@@ -1448,7 +1448,7 @@ def test_512_thread_geometry_on_biased_offsets_takes_pairs_of_12_to_20_kb(oracle
 
 def test_span_geometry_long_pairs_against_oracle(oracle):
     """The packed band kernel's 1024-thread geometry (16 waves x 5 chunk slots, offsets biased by the target length so that targets of up
-    to ~60 kb fit 16 bits, mwf_band2.hip wide_bias): pairs of 20-60 kb whose windows stay below 20 000 columns, s, n_iter and CIGAR
+    to ~60 kb fit 16 bits, mwf_band2_kernel.h wide_bias): pairs of 20-60 kb whose windows stay below 20 000 columns, s, n_iter and CIGAR
     against the oracle — default penalties, the (e1, e2) = (1, 1) and (2, 2) instantiations, a stop rule inside the pass."""
     specs = [(50000, 0.03, 0, 0), (50000, 0.02, 0, 0), (40000, 0.035, 0, 0), (33000, 0.04, 0, 0), (20000, 0.06, 0, 0), (60000, 0.008, 0, 0),
              (50000, 0.034, 0, 0), (25000, 0.05, 0, 0), (45000, 0.02, 3, 2500)]
