@@ -228,6 +228,50 @@ int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int
 /* The summary array and the maps are allocated on first use through the engine's accounting (mwf_gpu_stats_t dev_bytes / dev_bytes_peak
  * include them while the batch lives) and freed with the batch; a caller that never asks pays nothing. */
 
+/* ---- Alignment text: the form in which an alignment leaves a mapper (kernels: csrc/mwf_cigar_text.hip) ---- */
+
+/* The six products (`kind`).  The target plays SAM's reference. */
+#define MWF_TXT_CIGAR 0 /* the CIGAR as the reference's CLI prints it */
+#define MWF_TXT_SAM   1 /* SAM's M-form */
+#define MWF_TXT_CS    2 /* minimap2's cs tag (short form) */
+#define MWF_TXT_MD    3 /* SAM's MD tag */
+#define MWF_TXT_ROW_T 4 /* the gapped target row */
+#define MWF_TXT_ROW_Q 5 /* the gapped query row */
+#define MWF_TXT_KINDS 6
+/* Renderable: words are renderable for a pair iff every op is one of 1 I, 2 D, 7 =, 8 X, every length is >= 1, no word runs past a sequence
+ * (rules (a) and (b) of first_bad above) and the words end exactly at (tl, ql).  Bases under = and X are not compared (that is summarize's job).
+ * Decimal numbers have no leading zeros and no sign; sums are formed in 64 bits.  No terminators, no separators.
+ *   0 CIGAR  per word <len><c>, c = "MIDNSHP=X"[op]
+ *   1 SAM    a maximal run of consecutive words with op = or X becomes one <sum>M; I and D words are printed per word and never merged
+ *   2 cs     per word: = gives :<len>; X gives *<t><q> for each base; I gives + and the query bases; D gives - and the target bases.  Bytes
+ *            'A'..'Z' are lowered (b | 0x20), every other byte is copied verbatim
+ *   3 MD     a running count c of bases under =.  Every base under X: c (also when it is 0), the target byte verbatim, c = 0.  Every D word:
+ *            c, '^', its target bytes verbatim, c = 0.  I words are invisible (c runs across them).  At the end: c — a pair of two empty
+ *            sequences (no words) has the MD "0"
+ *   4, 5 rows  one byte per alignment column in word order, bytes verbatim; the target row (4) has '-' under I, the query row (5) '-' under
+ *            D; both are n_eq + n_x + n_ins + n_del bytes long
+ * 10= 1X 3D 8= 2I 12= on ACGTTGCAACGCATGGATCCTACGATCGGATTAC / ACGTTGCAACTGGATCCTATTCGATCGGATTAC:  10=1X3D8=2I12=  11M3D8M2I12M
+ * :10*gt-cat:8+tt:12  10G0^CAT20  ACGTTGCAACGCATGGATCCTA--CGATCGGATTAC  ACGTTGCAACT---GGATCCTATTCGATCGGATTAC */
+
+/* The host twin: text `kind` of one CIGAR against one pair.  Returns the full length of the text, snprintf-style (it may exceed cap); at most
+ * cap bytes are written; dst may be NULL when cap is 0.  Returns -1 and writes nothing when the words are not renderable or kind is out of
+ * range.  Needs no device.  Never reads outside ts[0,tl) / qs[0,ql), whatever the words say. */
+int64_t mwf_cigar_text(int32_t kind, int32_t n_cigar, const uint32_t *cigar, int32_t tl, const char *ts, int32_t ql, const char *qs,
+                       char *dst, int64_t cap);
+
+/* The device form: text `kind` of every pair into a library-owned pool, pair i's text at txt[off[i] .. off[i + 1]), off int64[n + 1] on the
+ * device.  A sizing launch, a device-side scan into off, one host wait for the total, the pool's allocation, then the writing launch is
+ * enqueued and the call returns.  d_words, d_word_off, d_n_words all NULL: the batch's own CIGARs (finalises; fails after a score-only
+ * align); otherwise foreign device arrays for the batch's sequences under the trust rules of mwf_gpu_batch_summarize.  Stopped pairs
+ * (status != 0), foreign pairs with d_n_words[i] <= 0 and pairs whose words are not renderable get empty text (off[i] == off[i + 1]; their MD
+ * is empty too); unrenderable words never cause an access outside the pair's sequences or its slice of the pool. */
+int mwf_gpu_batch_text(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t kind, const uint32_t *d_words, const int64_t *d_word_off, const int32_t *d_n_words);
+/* Device pointer to that text, its n + 1 offsets and the total bytes (d_off / total may be NULL); NULL before the first mwf_gpu_batch_text(.., kind, ..)
+ * and after a newer align.  One pool per kind, counted in dev_bytes / dev_bytes_peak, freed with the batch. */
+const char *mwf_gpu_batch_dev_text(const mwf_gpu_batch_t *b, int32_t kind, const int64_t **d_off, int64_t *total);
+/* Wait and copy the text (total bytes) to host_out and its n + 1 offsets to host_off (either may be NULL). */
+int mwf_gpu_batch_text_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t kind, char *host_out, int64_t *host_off);
+
 /* ---- Alphabet classes (kernels: csrc/mwf_alphabet.hip) ---- */
 
 /* The class of one pair by the bytes that occur in target and query together: 0 every byte is one of A C G T (upper case; two empty sequences

@@ -23,6 +23,8 @@ MWF_F_CIGAR = 0x1
 MWF_F_NO_KALLOC = 0x2
 MWF_F_DEBUG = 0x10000
 CIGAR_CHARS = "MIDNSHP=XBid"  # reference main.c:78
+# the six text products of a CIGAR (include/miniwfa.h): CIGAR string, SAM M-form, cs tag, MD tag, gapped target row, gapped query row
+MWF_TXT_CIGAR, MWF_TXT_SAM, MWF_TXT_CS, MWF_TXT_MD, MWF_TXT_ROW_T, MWF_TXT_ROW_Q, MWF_TXT_KINDS = 0, 1, 2, 3, 4, 5, 6
 
 
 class MwfOpt(C.Structure):
@@ -76,6 +78,7 @@ ABI_SYMBOLS = (
     "mwf_gpu_debug_band",
     "mwf_cigar_summary", "mwf_gpu_batch_dev_cigars", "mwf_gpu_batch_summarize", "mwf_gpu_batch_dev_summary", "mwf_gpu_batch_summary",
     "mwf_gpu_batch_map", "mwf_gpu_batch_dev_map", "mwf_gpu_batch_map_fetch",
+    "mwf_cigar_text", "mwf_gpu_batch_text", "mwf_gpu_batch_dev_text", "mwf_gpu_batch_text_fetch",
     "mwf_alphabet_class", "mwf_alphabet_class16", "mwf_gpu_batch_alphabet",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
@@ -172,6 +175,14 @@ def lib() -> C.CDLL:
     L.mwf_gpu_batch_dev_map.restype = C.c_void_p
     L.mwf_gpu_batch_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.mwf_gpu_batch_map_fetch.restype = C.c_int
+    L.mwf_cigar_text.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64]
+    L.mwf_cigar_text.restype = C.c_int64
+    L.mwf_gpu_batch_text.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_text.restype = C.c_int
+    L.mwf_gpu_batch_dev_text.argtypes = [C.c_void_p, C.c_int32, P(C.c_void_p), P(C.c_int64)]
+    L.mwf_gpu_batch_dev_text.restype = C.c_void_p
+    L.mwf_gpu_batch_text_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_text_fetch.restype = C.c_int
     L.mwf_alphabet_class.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p]
     L.mwf_alphabet_class.restype = C.c_int32
     L.mwf_alphabet_class16.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_void_p]
@@ -333,6 +344,19 @@ def cigar_summary(t: bytes, q: bytes, opt: MwfOpt, cigar: Sequence[int]) -> np.v
     out = AlnSummary()
     lib().mwf_cigar_summary(C.byref(opt), len(words), words.ctypes.data if len(words) else None, len(t), t, len(q), q, C.byref(out))
     return np.frombuffer(bytes(out), dtype=SUMMARY_DTYPE)[0]
+
+
+def cigar_text(kind: int, t: bytes, q: bytes, cigar: Sequence[int]) -> bytes | None:
+    """mwf_cigar_text, the host twin of Batch.texts(): text `kind` (MWF_TXT_*) of `cigar` (words len<<4|op) against (t, q); None when the words are
+    not renderable for the pair or kind is out of range.  Needs no device."""
+    words = np.ascontiguousarray(np.asarray(cigar, dtype=np.uint32))
+    wp = words.ctypes.data if len(words) else None
+    n = lib().mwf_cigar_text(kind, len(words), wp, len(t), t, len(q), q, None, 0)
+    if n < 0:
+        return None
+    buf = C.create_string_buffer(max(1, n))
+    lib().mwf_cigar_text(kind, len(words), wp, len(t), t, len(q), q, buf, n)
+    return buf.raw[:n]
 
 
 def alphabet_class(t: bytes, q: bytes):
@@ -547,6 +571,38 @@ class Batch:
     def dev_map_ptr(self, which: int) -> int | None:
         """Device pointer to the map of the last map(which); None before the first one and after a newer align."""
         return lib().mwf_gpu_batch_dev_map(self.h, which)
+
+    def text(self, kind: int, cigars=None):
+        """Enqueue the text kernels (mwf_gpu_batch_text; kind: MWF_TXT_*) and return; dev_text(kind) then points at the text.  cigars: None for the
+        batch's own CIGARs, or (words_ptr, off_ptr, n_words_ptr) device arrays of foreign ones, as in summarize()."""
+        w, o, c = cigars if cigars is not None else (None, None, None)
+        rc = lib().mwf_gpu_batch_text(self.eng.h, self.h, kind, w, o, c)
+        if rc != 0:
+            raise RuntimeError(f"text failed ({rc}): " + self.eng.error())
+
+    def text_fetch(self, kind: int):
+        """Wait for the last text(kind) and copy it -> (text[bytes], offsets[int64, n + 1]): pair i's text is text[offsets[i]:offsets[i + 1]]."""
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        rc = lib().mwf_gpu_batch_text_fetch(self.eng.h, self.h, kind, None, off.ctypes.data)
+        buf = np.zeros(max(1, int(off[-1])), dtype=np.uint8)
+        if rc == 0 and off[-1] > 0:
+            rc = lib().mwf_gpu_batch_text_fetch(self.eng.h, self.h, kind, buf.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError(f"text download failed ({rc}): " + self.eng.error())
+        return buf.tobytes()[:int(off[-1])], off
+
+    def texts(self, kind: int, cigars=None) -> list[bytes]:
+        """text() + wait + copy: one bytes object per pair (empty for a pair without a CIGAR or with unrenderable words)."""
+        self.text(kind, cigars)
+        raw, off = self.text_fetch(kind)
+        return [raw[off[i]:off[i + 1]] for i in range(self.n)]
+
+    def dev_text(self, kind: int):
+        """(text_ptr, off_ptr, total) of the last text(kind): pair i's text is the bytes [off[i], off[i + 1]) from text_ptr on, off int64[n + 1] on the
+        device, total = off[n]; None before the first text(kind) and after a newer align."""
+        off, total = C.c_void_p(), C.c_int64()
+        p = lib().mwf_gpu_batch_dev_text(self.h, kind, C.byref(off), C.byref(total))
+        return (p, off.value or 0, total.value) if p else None
 
     def work_sketch(self) -> np.ndarray:
         """hits[i]: 8-mers of pair i's query that occur in its target — the per-pair work estimate the band classes are dealt by (test hook)."""

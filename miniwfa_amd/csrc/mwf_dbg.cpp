@@ -173,4 +173,79 @@ void mwf_cigar_summary(const mwf_opt_t *opt, int32_t n_cigar, const uint32_t *ci
 	out->n_words = n_cigar, out->first_bad = first_bad, out->flags = 1;
 }
 
+// Host twin of the device text (mwf_cigar_text.hip): the six products by the rule table in include/miniwfa.h.  The words are checked first
+// (known op, length >= 1, inside both sequences, ending at (tl, ql)), so the rendering below only ever indexes ts[0,tl) / qs[0,ql).
+namespace {
+struct TextOut { // counts every byte, stores the first `cap` of them
+	char *dst;
+	int64_t cap, n;
+	void put(char c) { if (n < cap) dst[n] = c; ++n; }
+	void num(uint64_t v)
+	{
+		char buf[20];
+		int k = 0;
+		do buf[k++] = (char)('0' + v % 10), v /= 10; while (v);
+		while (k) put(buf[--k]);
+	}
+};
+inline char cs_lower(char b) { return b >= 'A' && b <= 'Z' ? (char)(b | 0x20) : b; }
+}
+
+int64_t mwf_cigar_text(int32_t kind, int32_t n_cigar, const uint32_t *cigar, int32_t tl, const char *ts, int32_t ql, const char *qs,
+                       char *dst, int64_t cap)
+{
+	if (kind < 0 || kind >= MWF_TXT_KINDS || tl < 0 || ql < 0) return -1;
+	if (n_cigar < 0) n_cigar = 0;
+	if (cap < 0) cap = 0;
+	int64_t ti = 0, qj = 0;
+	for (int32_t w = 0; w < n_cigar; ++w) {
+		const int32_t op = (int32_t)(cigar[w] & 0xf);
+		const int64_t len = (int64_t)(cigar[w] >> 4);
+		if ((op != 1 && op != 2 && op != 7 && op != 8) || len < 1) return -1;
+		if (op != 1) ti += len;
+		if (op != 2) qj += len;
+		if (ti > tl || qj > ql) return -1;
+	}
+	if (ti != tl || qj != ql) return -1;
+	TextOut o{dst, cap, 0};
+	uint64_t run = 0; // SAM: the open M run; MD: the open count of bases under '='
+	ti = qj = 0;
+	for (int32_t w = 0; w < n_cigar; ++w) {
+		const int32_t op = (int32_t)(cigar[w] & 0xf);
+		const int64_t len = (int64_t)(cigar[w] >> 4);
+		const bool both = op == 7 || op == 8;
+		switch (kind) {
+		case MWF_TXT_CIGAR: o.num((uint64_t)len), o.put("MIDNSHP=X"[op]); break;
+		case MWF_TXT_SAM:
+			if (both) {
+				run += (uint64_t)len;
+				if (w + 1 == n_cigar || ((cigar[w + 1] & 0xf) != 7 && (cigar[w + 1] & 0xf) != 8)) o.num(run), o.put('M'), run = 0;
+			} else o.num((uint64_t)len), o.put(op == 1 ? 'I' : 'D');
+			break;
+		case MWF_TXT_CS:
+			if (op == 7) o.put(':'), o.num((uint64_t)len);
+			else if (op == 8) for (int64_t k = 0; k < len; ++k) o.put('*'), o.put(cs_lower(ts[ti + k])), o.put(cs_lower(qs[qj + k]));
+			else {
+				o.put(op == 1 ? '+' : '-');
+				for (int64_t k = 0; k < len; ++k) o.put(cs_lower(op == 1 ? qs[qj + k] : ts[ti + k]));
+			}
+			break;
+		case MWF_TXT_MD:
+			if (op == 7) run += (uint64_t)len;
+			else if (op == 8) for (int64_t k = 0; k < len; ++k) o.num(run), o.put(ts[ti + k]), run = 0;
+			else if (op == 2) {
+				o.num(run), o.put('^'), run = 0;
+				for (int64_t k = 0; k < len; ++k) o.put(ts[ti + k]);
+			}
+			break;
+		case MWF_TXT_ROW_T: for (int64_t k = 0; k < len; ++k) o.put(op == 1 ? '-' : ts[ti + k]); break;
+		default:            for (int64_t k = 0; k < len; ++k) o.put(op == 2 ? '-' : qs[qj + k]); break;
+		}
+		if (op != 1) ti += len;
+		if (op != 2) qj += len;
+	}
+	if (kind == MWF_TXT_MD) o.num(run);
+	return o.n;
+}
+
 } // extern "C"

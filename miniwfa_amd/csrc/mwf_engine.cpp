@@ -188,6 +188,7 @@ void mwf_gpu_batch_free(mwf_gpu_batch_t *b)
 	give_block(g, g->spare_block, b->block);
 	give_block(g, g->spare_cig, b->cig);
 	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1], &b->alpha_cls, &b->alpha_arena}) release(g, *d); // (hipFree waits for a kernel still writing them)
+	for (int k = 0; k < MWF_TXT_KINDS; ++k) release(g, b->ops_text[k]), release(g, b->ops_text_off[k]);
 	delete b;
 }
 
@@ -347,6 +348,59 @@ int mwf_gpu_batch_map_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which, int
 	if (host_off) memcpy(host_off, off.data(), off.size() * 8);
 	if (!host_out || b->n == 0) { HIP_TRY(g, hipStreamSynchronize(g->stream)); return 0; }
 	return download(g, host_out, b->ops_map[which].p, (size_t)off[b->n] * 4);
+}
+
+/* ------------------------------------------------------------------ alignment text (mwf_cigar_text.hip) */
+
+int mwf_gpu_batch_text(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t kind, const uint32_t *d_words, const int64_t *d_word_off, const int32_t *d_n_words)
+{
+	if (!g || !b) return -1;
+	if (kind < 0 || kind >= MWF_TXT_KINDS) { g->err = "mwf_gpu_batch_text: kind must be one of MWF_TXT_* (0 .. 5)"; return -2; }
+	(void)hipSetDevice(g->device);
+	const bool own = !d_words && !d_word_off && !d_n_words;
+	if (!own && (!d_words || !d_word_off || !d_n_words)) { g->err = "mwf_gpu_batch_text: foreign CIGARs need all three device arrays (words, offsets, counts)"; return -2; }
+	if (own) { if (int rc = own_cigars(g, b, "mwf_gpu_batch_text")) return rc; }
+	else if (b->busy) HIP_TRY(g, hipStreamSynchronize(g->stream)); // (as mwf_gpu_batch_summarize)
+	b->text_valid[kind] = false;
+	DevBuf &off = b->ops_text_off[kind], &pool = b->ops_text[kind];
+	if (ensure(g, off, ((size_t)b->n + 1) * 8)) return -1;
+	CigarTextArgs a{};
+	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql, a.n_pairs = b->n;
+	a.words = b->d_cig_pool, a.word_off = b->d_cigoff, a.n_words = b->d_ncig, a.status = b->d_status;
+	if (!own) a.words = d_words, a.word_off = d_word_off, a.n_words = d_n_words, a.status = nullptr;
+	a.kind = kind, a.off = (int64_t*)off.p;
+	const int block = ops_block(b);
+	// sizes, offsets, and the one wait: the pool's size is only known on the device
+	a.mode = 0;
+	if (launch_cigar_text(a, block, g->stream) || launch_text_scan(a.off, b->n, g->stream)) { g->err = "kernel launch failed (alignment text, sizing)"; return -1; }
+	int64_t total = 0;
+	if (int rc = download(g, &total, a.off + b->n, 8)) return rc;
+	if (total < 0) { g->err = "mwf_gpu_batch_text: negative text size"; return -1; }
+	if (ensure(g, pool, std::max<size_t>((size_t)total, 256))) return -1;
+	a.mode = 1, a.txt = (char*)pool.p;
+	if (launch_cigar_text(a, block, g->stream)) { g->err = "kernel launch failed (alignment text)"; return -1; }
+	b->text_total[kind] = total;
+	b->text_valid[kind] = true;
+	return 0;
+}
+
+const char *mwf_gpu_batch_dev_text(const mwf_gpu_batch_t *b, int32_t kind, const int64_t **d_off, int64_t *total)
+{
+	if (!b || kind < 0 || kind >= MWF_TXT_KINDS || !b->text_valid[kind]) return nullptr;
+	if (d_off) *d_off = (const int64_t*)b->ops_text_off[kind].p;
+	if (total) *total = b->text_total[kind];
+	return (const char*)b->ops_text[kind].p;
+}
+
+int mwf_gpu_batch_text_fetch(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t kind, char *host_out, int64_t *host_off)
+{
+	if (!g || !b || kind < 0 || kind >= MWF_TXT_KINDS) return -1;
+	(void)hipSetDevice(g->device);
+	if (!b->text_valid[kind]) { g->err = "mwf_gpu_batch_text_fetch: no text of this kind (call mwf_gpu_batch_text after the align)"; return -2; }
+	if (host_off) { if (int rc = download(g, host_off, b->ops_text_off[kind].p, ((size_t)b->n + 1) * 8)) return rc; }
+	if (host_out && b->text_total[kind] > 0) return download(g, host_out, b->ops_text[kind].p, (size_t)b->text_total[kind]);
+	HIP_TRY(g, hipStreamSynchronize(g->stream));
+	return 0;
 }
 
 /* ------------------------------------------------------------------ alphabet classes ("alpha_remap"; mwf_alphabet.hip, alpha_prepare in mwf_memory.cpp) */

@@ -216,6 +216,10 @@ struct mwf_gpu_batch_s {
 	bool summary_valid = false, map_valid[2] = {false, false};
 	std::vector<int64_t> h_map_off[2]; // n + 1 offsets into the map (which 0: prefix sums of ql, 1: of tl); empty until first asked for
 	bool map_off_uploaded[2] = {false, false}; // ops_map_off[which] holds h_map_off[which] (set only after the upload succeeded)
+	// products of mwf_cigar_text.hip: one pool and one offset array (n + 1 int64) per kind, same lifetime
+	DevBuf ops_text[MWF_TXT_KINDS], ops_text_off[MWF_TXT_KINDS];
+	bool text_valid[MWF_TXT_KINDS] = {false, false, false, false, false, false};
+	int64_t text_total[MWF_TXT_KINDS] = {0, 0, 0, 0, 0, 0}; // bytes of text in the pool
 	int64_t ops_max_len = -1;          // longest pair (tl + ql): what the workgroup size of those kernels is chosen by (-1: not computed yet)
 };
 

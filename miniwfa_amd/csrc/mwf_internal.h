@@ -164,6 +164,23 @@ struct CigarOpsArgs {
 };
 int cigar_ops_block(int64_t max_len);                 // threads per pair for a batch whose longest pair has max_len bases of target + query
 int launch_cigar_ops(const CigarOpsArgs &a, int block, void *stream);
+// mwf_cigar_text.hip: the CIGARs of a batch as text (MWF_TXT_*; one workgroup per pair at the block size of cigar_ops_block(); off the align path)
+struct CigarTextArgs {
+	const uint8_t *seqs;
+	const int64_t *t_off, *q_off;
+	const int32_t *tl, *ql;
+	int32_t n_pairs;
+	const uint32_t *words;     // as in CigarOpsArgs
+	const int64_t *word_off;
+	const int32_t *n_words;
+	const int32_t *status;
+	int32_t kind;              // MWF_TXT_*
+	int32_t mode;              // 0: size — off[1 + i] = bytes of pair i's text (0: no CIGAR, or not renderable); 1: write pair i's text to txt[off[i], off[i + 1])
+	int64_t *off;              // [n_pairs + 1]
+	char *txt;                 // mode 1
+};
+int launch_cigar_text(const CigarTextArgs &a, int block, void *stream);
+int launch_text_scan(int64_t *off, int32_t n, void *stream); // off[1 .. n] lengths -> off[0 .. n] offsets (exclusive prefix sums; off[n]: the total); one workgroup
 // mwf_alphabet.hip: per-pair alphabet classes and the remapped copies of four-letter pairs ("alpha_remap"; one workgroup per pair; off the align path)
 struct AlphabetArgs {
 	const uint8_t *seqs;

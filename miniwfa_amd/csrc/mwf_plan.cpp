@@ -689,7 +689,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	(void)hipSetDevice(g->device);
 	b->opt = *opt;
 	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
-	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false; // (summaries and maps describe the previous align's CIGARs)
+	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
 	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
 	g->stats = mwf_gpu_stats_t{};
 	if (b->n == 0) { b->aligned = b->finalized = true, b->alpha_known = g->alpha_remap != 0; return 0; } // (an empty batch: nothing to classify or copy, and with "alpha_remap" 1 its zero classes are known)
