@@ -58,7 +58,7 @@ static void trim(mwf_gpu_t *g)
 {
 	(void)hipStreamSynchronize(g->stream);
 	for (DevBuf *b : {&g->ring, &g->sring, &g->good, &g->tb, &g->row_off, &g->row_lo, &g->cig_scratch, &g->snap, &g->snap_meta, &g->seg, &g->dbg,
-	                  &g->coop_edge, &g->coop_misc, &g->sys_box, &g->sys_prog, &g->sys_log, &g->sys_ep, &g->sys_park, &g->sys_ring, &g->sys_sring, &g->sys_good, &g->retry_ids,
+	                  &g->coop_misc, &g->sys_box, &g->sys_prog, &g->sys_log, &g->sys_ep, &g->sys_park, &g->sys_ring, &g->sys_sring, &g->sys_good, &g->retry_ids,
 	                  &g->spare_block, &g->spare_cig})
 		release(g, *b);
 	g->dev_bytes_peak = g->dev_bytes;

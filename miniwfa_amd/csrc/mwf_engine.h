@@ -15,10 +15,12 @@
 #include <cmath>
 #include <functional>
 #include <thread>
+#include <tuple>
 #include <vector>
 #include "miniwfa.h"
 #include "kalloc.h"
 #include "mwf_internal.h"
+#include "mwf_plan_classes.h"
 
 namespace mwf {
 namespace host {
@@ -47,6 +49,20 @@ constexpr int kMaxDevices = 64;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What distinguishes two kernel variants for the occupancy query (cached_occupancy, mwf_plan.cpp).  kind 2: the band family, 0: the generic kernel; the
+// fields of the other family stay zero.
+struct OccKey {
+	int kind = 0, block = 0;
+	// band family
+	int packed = 0, lane = 0, slots512 = 0, e1 = 0, e2 = 0, lds_bytes = 0; // slots512: span / 2048 of the 512-thread geometry (its chunk slots per wave: 3 ... 6), else 0
+	bool cigar = false, seq2 = false, tab = false, nib = false;
+	// generic kernel
+	bool stream_pass = false, ring16 = false, big_ring = false;
+	int lds_e2_cols = 0;
+	auto tied() const { return std::tie(kind, block, packed, lane, slots512, e1, e2, lds_bytes, cigar, seq2, tab, nib, stream_pass, ring16, big_ring, lds_e2_cols); }
+	bool operator<(const OccKey &o) const { return tied() < o.tied(); }
+};
+
 
 } // namespace host
 } // namespace mwf
@@ -65,8 +81,6 @@ struct mwf_gpu_s {
 	// tunables
 	int block = 0;              // 0: choose from the batch
 	bool dev_retry = true;      // batches of reads: the pairs the lane kernel hands back are re-run by a follow-up launch from a device-side list, without the host
-	int retry_mode = 0;         // set around run_batch_kernel(): 1 the launch fills the list, 2 the launch takes its pairs from it
-	int retry_slot = 0;         // ... which of the batch's kRetrySlots lists
 	bool band_fold = true;      // packed band kernel: the folded score-only form where the penalties allow it (o1 == x)
 	bool probe_table = true;    // packed band kernel: the table form of the first probe (mwf_band2_tab.hip) where it applies and two workgroups still share a CU (0: never)
 	int64_t probe_table_lds = 0; // mwf_gpu_test_hook "probe_table_lds": LDS bytes (table + sequence copies) above which a launch keeps the plain form (0: 74 KB, choose_kernel) — tests of the fall-back
@@ -89,12 +103,9 @@ struct mwf_gpu_s {
 	int wide_slots = 0;        // chunk slots per wave of the 512-thread packed geometry: 0 by batch (four until an align has shown that three hold every pair), 3, 4
 	int band_span = 1;         // the 1024-thread geometry of the packed band kernel (80 chunks, biased offsets: pairs of up to ~60 kb whose windows stay below ~20 000 columns): 0 never, 2: every pair it can take (tests)
 	int ring16 = 1;            // generic kernel with E2/F2 in LDS: 16-bit ring rows in HBM while target length + penalty fits 16 bits (0: never)
-	bool ring16_off_once = false; // set around the re-run of pairs whose offsets outgrew 16 bits
 	int seq2bit = 1;           // packed band kernel: 2-bit sequence copy in LDS for pairs of plain A/C/G/T (0: always bytes)
-	bool acgt_off_once = false; // set around the re-run of pairs that are not plain ACGT
 	int alpha_remap = 0;       // 1: pairs of at most four distinct bytes are copied into a per-batch arena with their bytes mapped onto A/C/G/T and planned as plain pairs (alpha_prepare, mwf_memory.cpp); 0: never
 	int alpha16 = 0;           // 1 (with alpha_remap 1 only): pairs of 5 to 16 distinct bytes are class 3, copied as 0x40 | code, and take the packed band kernel's 4-bit form under gap extensions (2,1)
-	bool nib_once = false;     // set around a launch whose pairs are all class 3 on the 4-bit route: choose_kernel picks the 4-bit geometries (as acgt_off_once picks the byte-wise one)
 	int64_t alpha_arena_budget = -1; // mwf_gpu_test_hook "alpha_arena_budget": bytes an arena may take (-1: four fifths of what is free) — tests of the fall-back
 	int lds_e2 = 1;            // generic kernel: keep E2/F2 in LDS where that applies (0: never)
 	int scalar_generic = 0;    // 1: the generic kernel's original one-column-per-lane pass everywhere (comparison / fallback)
@@ -105,7 +116,7 @@ struct mwf_gpu_s {
 	int sys_p = 8;             // whole-device (systolic) kernel: penalties per hand-off block (4, 8 or 16)
 	int sys_c = 0;             // its columns per lane: 0 automatic (1 while the window is expected to fit the slots that way, else 4), 1, 4
 	// workspace (per-stream pool)
-	DevBuf ring, sring, good, tb, row_off, row_lo, cig_scratch, snap, snap_meta, seg, queue, dbg, coop_edge, coop_misc;
+	DevBuf ring, sring, good, tb, row_off, row_lo, cig_scratch, snap, snap_meta, seg, queue, dbg, coop_misc;
 	DevBuf retry_ids;          // pair ids of a re-run (finalize): kept by the engine — round 4 allocated and freed one per re-run, a hipMalloc + hipFree of ~0.15 ms behind a 0.5 ms launch
 	DevBuf sys_box, sys_prog, sys_log, sys_ep, sys_park, sys_ring, sys_sring, sys_good;
 	DevBuf spare_block, spare_cig; // allocations of freed batches, waiting for the next batch
@@ -125,7 +136,7 @@ struct mwf_gpu_s {
 	bool alpha_timed[2] = {false, false};                           // ... which of them that align made
 	mwf_gpu_stats_t stats{};
 	int64_t dev_bytes = 0, dev_bytes_peak = 0; // device memory this engine holds right now / held at most since the last "trim"
-	std::map<uint64_t, int> occ_cache;         // kernel variant -> resident workgroups per CU
+	std::map<OccKey, int> occ_cache;           // kernel variant -> resident workgroups per CU
 	int coop_grid = -1;
 	int coop_grid_cap = 0;      // "coop_grid": at most this many workgroups for the whole-device kernel (0: one per CU)
 };
@@ -145,7 +156,8 @@ struct mwf_gpu_batch_s {
 	int32_t *d_order = nullptr;
 	std::vector<int32_t> h_order;   // what d_order holds: pair ids, grouped by size class, longest first inside a class
 	std::vector<int32_t> h_len_order; // pair ids, longest pair first (stable): what every grouping is dealt from
-	std::vector<int8_t> h_class;    // size class of every pair (0 generic, then band kernels: 1 wide, 2 small, 3 tiny, 4 micro; 5: the 1024-thread span geometry)
+	std::vector<int8_t> h_class;    // where a pair that is handed back starts again, as a PairClass: CLS_GENERIC, one of the four band classes CLS_WIDE ... CLS_MICRO, or CLS_SPAN
+	                                // (the plan's PairPlan::fallback — a biased pair carries CLS_WIDE, a lane pair CLS_MICRO; finalize() moves it on with every re-route)
 	std::vector<int8_t> h_kind;     // kernel that ran the pair last (0 generic, 1 whole-device, 2 band)
 	float div_est = 0;              // divergence of the batch as a k-mer sketch of a few of its pairs saw it while the batch was built from host memory (0: unknown)
 	std::vector<int8_t> h_acgt;     // from the host's look at the bytes while a batch is built from host memory: 1 both sequences are plain
@@ -164,8 +176,7 @@ struct mwf_gpu_batch_s {
 	bool alpha_known = false;       // h_alpha describes the last align (mwf_gpu_batch_alphabet)
 	bool alpha_active = false;      // the last align read the copies
 	bool alpha_laid_out = false;    // the arena's offsets (and, uploaded batches, its copies) are in place for h_alpha
-	std::vector<int8_t> h_flags;    // bit 0: runs as high-memory although opt.step > 0 (its penalty bound is below step);
-	                                // bit 1: shared the whole-device kernel with other pairs; bit 2: walk variant of the low-memory mode
+	std::vector<int8_t> h_flags;    // FLAG_* (mwf_plan_classes.h): FLAG_STEP0 from the plan; the others say where the pair ran last, for finalize()'s re-routes
 	// results: one region of the block, fetched by one copy
 	unsigned long long *d_cig_head = nullptr;
 	int32_t *d_status = nullptr, *d_s = nullptr, *d_ncig = nullptr, *d_dbg4 = nullptr;
@@ -192,14 +203,14 @@ struct mwf_gpu_batch_s {
 	struct PlanCache {
 		bool valid = false;
 		int32_t opt_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-		int64_t tun_key[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		int64_t tun_key[3] = {0, 0, 0}; // the engine's tun_gen, the engine, the traced pair
 		int64_t max_len = 0, max_bound = 0;
 		bool has_groups = false, mid_bytes = false;
 		// The wide class (512-thread geometry) holds 24 chunks with three slots per wave and 32 with four (2 % slower where three suffice).  0: not known yet —
 		// four slots, and the kernel reports whether three would have held every pair; 1: three hold this batch under these options; 2: four are needed.
 		int8_t wide_state = 0;
 		bool wide_measured = false; // this align's first launch of the class ran on four slots with the report word zeroed
-		struct GI { int32_t n = 0; int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; } gi[17];
+		struct GI { int32_t n = 0; int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; } gi[kNumClasses];
 		std::vector<int8_t> cls0, flags0;
 	} plan;
 	std::vector<char> host_out;     // the fixed-size results as they came back (finalize)

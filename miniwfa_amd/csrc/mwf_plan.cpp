@@ -28,26 +28,10 @@ const char *validate(const mwf_opt_t &o)
 	return nullptr;
 }
 
-// Upper bound on the optimal penalty: delete the whole target, insert the whole query.
-int64_t penalty_bound(const mwf_opt_t &o, int64_t tl, int64_t ql, bool honour_max_s)
-{
-	auto gap = [&](int64_t L) -> int64_t { return L == 0 ? 0 : std::min<int64_t>(o.o1 + L * o.e1, o.o2 + L * o.e2); };
-	int64_t b = gap(tl) + gap(ql);
-	// the core pass stops one penalty after max_s (miniwfa.c:422); the low-memory first pass never stops (:569-589)
-	if (honour_max_s && o.max_s > 0) b = std::min<int64_t>(b, (int64_t)o.max_s + 1);
-	return b;
-}
+// Upper bound on the optimal penalty (mwf_plan_classes.h)
+int64_t penalty_bound(const mwf_opt_t &o, int64_t tl, int64_t ql, bool honour_max_s) { return penalty_bound(make_penalty(o), o.max_s, tl, ql, honour_max_s); }
 
-// widest window the 64-, 128- and 256-thread packed band variants are chosen for: (waves x 3 chunks - 1) x 256 - 64 columns
-constexpr int64_t kBandMicroWindow = (1 * 3 - 1) * 256 - 64, kBandTinyWindow = (2 * 3 - 1) * 256 - 64, kBandSmallWindow = (4 * 3 - 1) * 256 - 64;
-constexpr int64_t kBandWideWindow = (8 * 3 - 1) * 256 - 64;
-// The 512-thread geometry with FOUR chunk slots per wave (32 chunks, 119 VGPRs, still two workgroups per CU; 2-bit sequence copies only): 2 % slower than
-// three slots on windows those hold (1024 x 10 kb @ 5 %: 17.7 against 17.4 ms) — and 17.7 against 24.8 ms on a batch in which ONE pair outgrows them
-// late and is re-run alone (three of four seeds of that batch shape, profiles/r04/wide4.txt).  Taken when a forecast or the batch's last align says so.
-constexpr int64_t kBandWide4Window = (8 * 4 - 1) * 256 - 64;
-// ... and the 1024-thread span geometry (16 waves x kBand2SpanK chunks, offsets biased by the target length: mwf_band2_kernel.h wide_bias)
-constexpr int64_t kBandSpanMaxSeq = 62000;
-inline int64_t band_span_window() { return ((int64_t)band2_span_chunks() - 1) * 256 - 64; }
+inline int64_t band_span_window() { return band_window(band2_span_chunks()); }
 
 struct Plan {
 	int kind = 0;              // 0: generic kernel, 2: band kernel
@@ -59,31 +43,55 @@ struct Plan {
 	bool low_mem = false, cigar = false;
 };
 
+typedef mwf_gpu_batch_t::PlanCache::GI GroupInfo;
+
+// One launch of the one-workgroup-per-pair kernels, as its caller asks for it (run_batch_kernel).
+struct LaunchReq {
+	mwf_opt_t opt{};
+	const int32_t *d_order = nullptr; // the launch's pairs (device) ...
+	int32_t n_items = 0;              // ... and how many
+	int slots = 1 << 30;              // at most this many workgroups: as many as the chosen kernel can keep resident (retries ask for fewer, larger slots)
+	GroupInfo group;                  // the maxima over the launch's pairs
+	Geom geom = GEOM_CHOOSE;
+	CopyForm copy = COPY_2BIT;
+	int want_kind = -1;               // -1: the engine's "force_kind", 0 generic, 2 band
+	int64_t window_hint = 0;          // the widest window the pairs are expected to reach (0: unknown)
+	bool ring16_allowed = true;       // false: the re-run of pairs whose offsets outgrew the generic kernel's 16-bit ring rows
+	int retry_list = 0;               // re-runs without the host: 1 the launch fills the batch's device-side list, 2 the launch takes its pairs from it
+	int retry_slot = 0;               // ... which of the batch's kRetrySlots lists
+	bool report_wide = false;         // the wide class's measuring launch: four slots, and the kernel notes whether three would have held every pair
+	bool timed_begin = false, timed_end = false; // the events that bracket all launches of an align call (not the retries)
+};
+
 int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16 = false);
 
 // Which kernel serves a set of pairs.  The band kernel keeps E/F in registers and therefore only holds windows up to
-// its span; it has no low-memory first pass.  kind: -1 automatic, 0 generic, 2 band.
-void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t max_len, int64_t max_bound,
-                   int64_t max_seq_lds, int64_t max_tl, int want_kind, Plan &pl, int geom_block = 0, int64_t window_hint = 0)
+// its span; it has no low-memory first pass.
+void choose_kernel(mwf_gpu_t *g, const LaunchReq &rq, const Penalty &P, Plan &pl)
 {
+	const mwf_opt_t &opt = rq.opt;
+	const int want_kind = rq.want_kind >= 0 ? rq.want_kind : g->force_kind; // -1 automatic, 0 generic, 2 band
+	const int64_t max_len = rq.group.max_len, max_bound = rq.group.max_bound, max_seq_lds = rq.group.max_seq_lds, max_tl = rq.group.max_tl, window_hint = rq.window_hint;
+	Geom geom = rq.geom;
+	const bool bytes_only = rq.copy == COPY_BYTES; // pairs that are not plain ACGT: no 2-bit (or 4-bit) copies
 	pl.kind = 0;
 	const bool low_mem = (opt.flag & MWF_F_CIGAR) && opt.step > 0;
 	// packed band kernel (mwf_band2.hip): 16-bit offsets
 	const bool can_packed = band2_supported(P) && g->band_pack != 0;
-	if (geom_block == 32 && want_kind != 0 && !low_mem && lane_supported(P)) { // the short-pair class: one wave per pair, one diagonal per lane
+	if (geom == GEOM_LANE && want_kind != 0 && !low_mem && lane_supported(P)) { // the short-pair class: one wave per pair, one diagonal per lane
 		// The rows of all chunks are allocated whatever the window does, and LDS is what bounds the waves per CU (four chunks with the default
 		// penalties: 14.5 KB, eleven waves; three: thirteen).  Three hold penalties up to ~110: 40 000 x 150 bp @ 5 % 0.68 against 0.79 ms with one
 		// pair re-run, 20 000 x 200 bp 0.52 / 0.61 with ten, 20 000 x 150 bp @ 10 % 0.75 / 0.93 with 499 (profiles/r03/lane_kernel_probe.txt).
 		const int chunks = g->lane_chunks > 0 ? g->lane_chunks : max_len <= 400 ? 3 : 4;
 		// 2-bit sequence copies from ~450 bases of target + query on (measured: 20 000 x 250 bp 0.624 against 0.650 ms with byte copies, 40 000 x
 		// 150 bp 0.664 against 0.617 — packing costs more than the shorter extension trips save; profiles/r04/short_reads_step.txt)
-		BandGeom lg{64, 1, 64 * chunks, lane_lds_bytes(P, chunks, max_seq_lds), (g->seq2bit != 0 && !g->acgt_off_once && max_len >= 450) ? 1 : 0, 1};
+		BandGeom lg{64, 1, 64 * chunks, lane_lds_bytes(P, chunks, max_seq_lds), (g->seq2bit != 0 && !bytes_only && max_len >= 450) ? 1 : 0, 1};
 		if (lg.lds_bytes <= 60 * 1024) { // (deep rings — large gap-open costs — with a raised lane_max_len: the band classes below take the pairs)
 			pl.kind = 2, pl.band = lg;
 			return;
 		}
 	}
-	if (geom_block == 33 && want_kind != 0 && !low_mem && mid_supported(P)) { // a few mid-size pairs: one workgroup per pair, every ring in LDS (mwf_mid.hip)
+	if (geom == GEOM_MID && want_kind != 0 && !low_mem && mid_supported(P)) { // a few mid-size pairs: one workgroup per pair, every ring in LDS (mwf_mid.hip)
 		// the span: as many 64-column groups as the LDS holds beside the sequences (a window is about twice the final penalty wide: a 2 kb
 		// pair at 5 % needs ~1100 columns), never more than the widest possible window plus the dead margins
 		const int64_t want_cols = (std::min<int64_t>(max_len + 1, 2 * max_bound + 3) + 2 * P.nH + 63) / 64 * 64;
@@ -96,15 +104,15 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 			// (window_hint: the widest window the class's pairs are expected to reach — a pair of very different lengths opens a gap its length does not tell)
 			const int64_t by_len = window_hint > 0 ? std::max<int64_t>(max_len, window_hint * 100 / 28) : max_len;
 			const int block = g->mid_block ? g->mid_block : (by_len <= 1000 ? 256 : by_len <= 2500 ? 512 : 1024); // (4 x 400 bp: 131 us on four waves, 145 on eight)
-			const int seq2 = g->seq2bit != 0 && !g->acgt_off_once;
+			const int seq2 = g->seq2bit != 0 && !bytes_only;
 			pl.kind = 2, pl.band = BandGeom{block, 1, 64 * groups, lds, seq2, 2};
 			return;
 		}
 	}
 	if (want_kind == 0 || low_mem || !can_packed) return;
-	if (geom_block == 514) { // the 512-thread geometry with five / six chunk slots on biased offsets (the caller checked the lengths: kBandSpanMaxSeq); 2-bit copies only
+	if (geom == GEOM_BIASED) { // the 512-thread geometry with five / six chunk slots on biased offsets (the caller checked the lengths: kBandSpanMaxSeq); 2-bit copies only
 		const int64_t need_lds = ((max_len >> 4) + 4) * 4;
-		if (g->seq2bit == 0 || g->acgt_off_once || need_lds > 70 * 1024 || !band2_biased512_supported(P)) return;
+		if (g->seq2bit == 0 || bytes_only || need_lds > 70 * 1024 || !band2_biased512_supported(P)) return;
 		// (five chunk slots per wave while target + query stay below 3.5 of that span, else six)
 		// (... or when the class was admitted on a forecast window — divergence known, window_hint = the class's largest — that five slots cannot hold: the
 		// admission test is against the SIX-slot window, a 17 kb pair at 10 % must not start on five and overflow)
@@ -116,13 +124,13 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 		// fewer than two resident workgroups, and the pairs take the span geometry as they would without these copies.
 		pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
 		if (cached_occupancy(g, P, pl, 0, false) >= 2) return;
-		pl.kind = 0, pl.band = BandGeom{0, 0, 0, 0, 0, 0}, geom_block = 1024;
+		pl.kind = 0, pl.band = BandGeom{0, 0, 0, 0, 0, 0}, geom = GEOM_SPAN;
 	}
-	if (geom_block == 1024) { // the span geometry (the caller checked the lengths of every pair: kBandSpanMaxSeq); 2-bit sequence copies only
+	if (geom == GEOM_SPAN) { // the span geometry (the caller checked the lengths of every pair: kBandSpanMaxSeq); 2-bit sequence copies only
 		// ("alpha16", a launch of class-3 pairs: 4-bit copies — eight bases per dword, 62 000 bases per sequence about 62 KB)
-		const bool nib = g->nib_once && band2_nib_supported(P);
+		const bool nib = rq.copy == COPY_NIB && band2_nib_supported(P);
 		const int64_t need_lds = nib ? ((max_len >> 3) + 4) * 4 : ((max_len >> 4) + 4) * 4;
-		if (g->band_span == 0 || g->seq2bit == 0 || g->acgt_off_once || need_lds > 150 * 1024) return;
+		if (g->band_span == 0 || g->seq2bit == 0 || bytes_only || need_lds > 150 * 1024) return;
 		pl.kind = 2, pl.band = BandGeom{1024, 1, (int)band2_span_chunks() * 256, (int)((need_lds + 15) / 16 * 16), 1, 0, 0, nib ? 1 : 0};
 		return;
 	}
@@ -152,9 +160,9 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	// forced geometry (tests, tuning)
 	if (g->block == 64 || g->block == 128 || g->block == 256 || g->block == 512 || g->block == 768) bg.block = g->block;
 	// geometry picked by the caller for a size class (pairs short enough that their window should stay inside a small span)
-	if (g->block == 0 && (geom_block == 64 || geom_block == 128 || geom_block == 256)) bg.block = geom_block;
+	if (g->block == 0 && geom_small_block(geom)) bg.block = geom_small_block(geom);
 	// "alpha16", a launch of class-3 pairs: the 4-bit form exists on the 512-thread geometry (three or four slots) whatever the window class (a forced 768 stays byte-wise)
-	const bool nib = g->nib_once && g->seq2bit != 0 && !g->acgt_off_once && band2_nib_supported(P) && bg.block != 768;
+	const bool nib = rq.copy == COPY_NIB && g->seq2bit != 0 && !bytes_only && band2_nib_supported(P) && bg.block != 768;
 	if (nib) bg.block = 512;
 	bg.span = bg.block / 64 * (bg.block != 768 ? 3 : 2) * 256;
 	// (a forced 512-thread block with "wide_slots" 4: four slots whatever the window — tests of the four-slot kernels on short pairs)
@@ -164,7 +172,7 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 	const int64_t lds_cap = bg.block >= 768 ? 140 * 1024 : bg.block >= 512 ? 70 * 1024 : bg.block == 256 ? 36 * 1024 : bg.block == 128 ? 18 * 1024 : 9 * 1024;
 	// the packed kernel's sequence copy holds 2 bits per base unless that is switched off (or this is the re-run of pairs that
 	// are not plain ACGT): a quarter of the LDS, half the LDS instructions per probe
-	const bool seq2 = g->seq2bit != 0 && !g->acgt_off_once;
+	const bool seq2 = g->seq2bit != 0 && !bytes_only;
 	const int64_t need_lds = nib ? ((max_len >> 3) + 4) * 4 : seq2 ? ((max_len >> 4) + 4) * 4 : max_seq_lds;
 	bg.lds_bytes = need_lds <= lds_cap ? (int)((need_lds + 15) / 16 * 16) : 0;
 	bg.seq2 = seq2 && bg.lds_bytes > 0;
@@ -199,11 +207,11 @@ void choose_kernel(mwf_gpu_t *g, const mwf_opt_t &opt, const Penalty &P, int64_t
 // resident workgroups per CU of a kernel variant (one runtime query per variant and engine)
 int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16)
 {
-	uint64_t key;
-	if (pl.kind == 2)
-		key = 1ull | (uint64_t)pl.band.block << 4 | (uint64_t)(pl.band.packed == 1) << 16 | (uint64_t)(pl.band.packed == 2) << 15 | (uint64_t)(pl.band.lds_bytes > 0) << 17 | (uint64_t)pl.cigar << 18 |
-		      (uint64_t)(pl.band.seq2 != 0) << 3 | (uint64_t)(pl.band.lane == 1) << 2 | (uint64_t)(pl.band.block == 512 && pl.band.span > 6144) << 1 | (uint64_t)(pl.band.block == 512 ? pl.band.span / 2048 : 0) << 56 | (uint64_t)(pl.band.lane == 2) << 19 | (uint64_t)P.e1 << 20 | (uint64_t)P.e2 << 28 | (uint64_t)pl.band.lds_bytes << 36 | (uint64_t)(pl.band.tab > 0) << 62 | (uint64_t)(pl.band.nib != 0) << 63;
-	else key = 2ull | (uint64_t)pl.block << 4 | (uint64_t)stream_pass << 16 | (uint64_t)ring16 << 17 | (uint64_t)(P.nH > kMaxRing) << 18 | (uint64_t)lds_e2_cols << 20;
+	OccKey key;
+	if (pl.kind == 2) {
+		key.kind = 2, key.block = pl.band.block, key.packed = pl.band.packed, key.lane = pl.band.lane, key.slots512 = pl.band.block == 512 ? pl.band.span / 2048 : 0;
+		key.e1 = P.e1, key.e2 = P.e2, key.lds_bytes = pl.band.lds_bytes, key.cigar = pl.cigar, key.seq2 = pl.band.seq2 != 0, key.tab = pl.band.tab > 0, key.nib = pl.band.nib != 0;
+	} else key.block = pl.block, key.stream_pass = stream_pass, key.ring16 = ring16, key.big_ring = P.nH > kMaxRing, key.lds_e2_cols = lds_e2_cols;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;
 	const int per = pl.kind == 2 && pl.band.lane == 2 ? 1 // (mwf_mid.hip: most of a CU's LDS per workgroup)
@@ -231,19 +239,21 @@ int64_t tb_budget_bytes(mwf_gpu_t *g)
 // no other kernel of this process holds CUs while its workgroups wait for one another.
 std::shared_mutex g_dev_gate[kMaxDevices];
 
-// Run the one-workgroup-per-pair kernel over `n_items` pairs given by d_order (device) on at most `slots` workgroups.
-// tb_total_budget < 0: the traceback budget is looked up here, and only when the arena has to grow.
-int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const int32_t *d_order, int32_t n_items,
-                     int slots, int64_t max_len, int64_t max_bound, int64_t max_bound1, bool timed,
-                     int want_kind, int64_t max_tl, int64_t max_seq_lds, int timed_end, int geom_block, int *ran_kind, int64_t window_hint = 0)
+// Run the one-workgroup-per-pair kernel over the request's pairs on at most rq.slots workgroups; *ran_kind: the kernel that took them (0 generic, 2 band).
+// The traceback budget is looked up here, and only when the arena has to grow.
+int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *ran_kind)
 {
+	const mwf_opt_t &opt = rq.opt;
+	const int32_t n_items = rq.n_items;
+	const int64_t max_len = rq.group.max_len, max_bound = rq.group.max_bound, max_bound1 = rq.group.max_bound1, max_tl = rq.group.max_tl;
+	int slots = rq.slots;
 	const Penalty P = make_penalty(opt);
 	Plan pl;
 	pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
 	pl.low_mem = pl.cigar && opt.step > 0;
 	// generic kernel: four waves per pair, eight once the windows are wide (measured on 1250 x 50 kb: 708 ms against 782 ms)
 	pl.block = g->block > 0 && g->block != 768 ? g->block : (std::min<int64_t>(max_len + 1, 2 * max_bound + 3) >= 8192 ? 512 : 256);
-	choose_kernel(g, opt, P, max_len, max_bound, max_seq_lds, max_tl, want_kind >= 0 ? want_kind : g->force_kind, pl, geom_block, window_hint);
+	choose_kernel(g, rq, P, pl);
 	// `slots` is an upper bound from the caller (retries ask for fewer, larger slots); the chosen kernel's own residency
 	// bounds it as well
 	int per_cu, lds_e2_cols = 0;
@@ -266,7 +276,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 			// (round 5: where the batch's divergence is known — estimate_divergence — the penalty is guessed from it, ~5.2 per diverged base
 			// with the default costs plus a third: 50 kb pairs at 5 % reach penalty 12 500 and never fitted, 64 of 64 were run twice)
 			const int64_t s_guess = b->div_est > 0 && g->div_aware ? (int64_t)(6.9 * b->div_est * (double)max_tl) + 256 : max_len / 8;
-			ring16 = g->ring16 != 0 && !g->ring16_off_once && max_tl + std::max<int64_t>(s_guess, max_len / 8) < 65500;
+			ring16 = g->ring16 != 0 && rq.ring16_allowed && max_tl + std::max<int64_t>(s_guess, max_len / 8) < 65500;
 			// 32-bit: one workgroup per CU either way (128 KB of LDS): twelve waves fit its 168-VGPR budget, 490 ms against 519 ms with eight
 			// 16-bit: 512 threads, two workgroups per CU (64 KB of LDS each, 128 VGPRs) — 354 ms on 1250 x 50 kb against 375 ms for
 			// 768 threads and one per CU (479 ms with 32-bit rows); with traceback the 512-thread copy spills too much: 768 (451 against 477 ms)
@@ -284,10 +294,10 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 		const int64_t per_slot = (int64_t)(P.nH + 2 * P.n1 + 2 * P.n2) * ((max_len + 3 + 255) / 256 * 256 + 512) * 4 * (pl.low_mem ? 2 : 1);
 		slots = (int)std::max<int64_t>(1, std::min<int64_t>(slots, (int64_t)(g->total_mem / 10) / std::max<int64_t>(per_slot, 1)));
 	}
-	if (getenv("MWF_DEBUG"))
-		fprintf(stderr, "[libmwf_hip] kernel kind %d: block %d packed %d lds %d B, %d workgroup(s) per CU, %d slots, %d pairs\n", pl.kind, pl.block,
-		        pl.band.packed, pl.band.lds_bytes, per_cu, slots, n_items);
 	pl.grid = std::max(1, std::min<int>(slots, n_items));
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] kernel kind %d: block %d packed %d lds %d B, %d workgroup(s) per CU, %d slots, %d pairs; span %d seq2 %d lane %d tab %d nib %d grid %d hint %lld\n", pl.kind, pl.block,
+		        pl.band.packed, pl.band.lds_bytes, per_cu, slots, n_items, pl.band.span, pl.band.seq2, pl.band.lane, pl.band.tab, pl.band.nib, pl.grid, (long long)rq.window_hint);
 	// row stride: whole 256-column chunks plus room for the band kernel's neighbour loads past the last chunk
 	pl.W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512);
 	pl.GW = pl.W / 64 + 2;
@@ -339,7 +349,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
 	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
-	a.order = d_order, a.n_pairs = n_items;
+	a.order = rq.d_order, a.n_pairs = n_items;
 	a.timeline = g->timeline;
 	// A launch of one workgroup per pair on the kernels that take it (lane, mid, packed band) needs no work counter: workgroup i aligns
 	// pair i.  Otherwise a fresh counter: the first kQueueSlots launches of an align call use the ones its reset kernel zeroed.
@@ -359,8 +369,8 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 		HIP_TRY(g, hipMemsetAsync(g->queue.p, 0, 4, g->stream)); // (stream order: the launch that used it last is complete by then)
 	}
 	// re-runs without the host (BatchArgs::retry_ids): this launch fills the batch's list / takes its pairs from it
-	if (g->retry_mode == 1) a.retry_ids = b->d_retry_ids + g->retry_slot * kRetryCap, a.retry_cap = kRetryCap, a.retry_count = (unsigned int*)(b->d_cig_head + 2 + g->retry_slot);
-	if (g->retry_mode == 2) a.n_pairs_dev = (const unsigned int*)(b->d_cig_head + 2 + g->retry_slot), a.queue = nullptr, a.queue_parts = 0;
+	if (rq.retry_list == 1) a.retry_ids = b->d_retry_ids + rq.retry_slot * kRetryCap, a.retry_cap = kRetryCap, a.retry_count = (unsigned int*)(b->d_cig_head + 2 + rq.retry_slot);
+	if (rq.retry_list == 2) a.n_pairs_dev = (const unsigned int*)(b->d_cig_head + 2 + rq.retry_slot), a.queue = nullptr, a.queue_parts = 0;
 	a.scalar_generic = g->scalar_generic;
 	a.band_fold = g->band_fold ? 1 : 0;
 	a.lds_e2_cols = lds_e2_cols;
@@ -385,7 +395,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 	// one align can make several block-mode launches (size classes, byte-wise twins, re-runs): a launch the slack no longer covers takes words singly
 	a.cig_block = 0;
 	if (b->cig_block > 0 && pl.grid <= b->cig_block_left) a.cig_block = b->cig_block, b->cig_block_left -= pl.grid;
-	a.report_wide = geom_block == 0 && window_hint == kBandWide4Window ? 1 : 0; // (the wide class's measuring align, mwf_gpu_batch_align)
+	a.report_wide = rq.report_wide ? 1 : 0;
 	a.snap = pl.low_mem ? (int32_t*)g->snap.p : nullptr, a.snap_slot_ints = pl.snap_slot_ints;
 	a.snap_meta = pl.low_mem ? (int32_t*)g->snap_meta.p : nullptr, a.snap_meta_slot = pl.snap_meta_slot;
 	a.seg = pl.low_mem ? (int32_t*)g->seg.p : nullptr, a.seg_slot = pl.seg_slot;
@@ -395,7 +405,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 	a.dbg_cap = b->debug_pair >= 0 ? (int32_t)(g->dbg.bytes / 8) : 0;
 
 	// HIP events bracket the kernel only: every workspace allocation above is already done
-	if (timed) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
+	if (rq.timed_begin) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
 	std::shared_lock<std::shared_mutex> gate(g_dev_gate[g->device % kMaxDevices]); // not while a whole-device kernel runs
 	const int lrc = pl.kind == 2 && pl.band.lane == 2 ? launch_mid(a, pl.grid, pl.band.block, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
 	              : pl.kind == 2 && pl.band.lane ? launch_lane(a, pl.grid, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
@@ -407,7 +417,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, con
 		return -1;
 	}
 	b->last_grid = std::max(b->last_grid, pl.grid);
-	if (timed_end < 0 ? timed : timed_end != 0) { // the events bracket all launches of an align call, not the retries
+	if (rq.timed_end) { // the events bracket all launches of an align call, not the retries
 		HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
 		g->ev_pending = true;
 	}
@@ -465,8 +475,6 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	const int32_t W = (int32_t)((len + 3 + 255) / 256 * 256 + 512), GW = W / 64 + 2;
 	const int64_t TC = coop_chunk_slots(Gs);
 	const size_t NG = (size_t)n_groups;
-	// the systolic kernel (mwf_sys.hip) runs every pass but the provenance pass of the two-pass low-memory mode
-	const bool use_sys = true;
 	const int sysP = g->sys_p, sysP2 = g->sys_p;
 	// Columns per lane of the systolic kernel, per pass: one column per lane (64-column slots that own 48) quarters the
 	// per-column work a wave does per penalty — what a chain of penalties on a narrow window waits for — but needs five times
@@ -475,7 +483,7 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	// outgrows the slots comes back as ST_BAND_OVERFLOW and is re-run with four columns per lane (finalize()).
 	auto window_cap = [&](int c) -> int64_t { return (TC - 4) * (int64_t)sys_owned_cols(sysP, c) - 2 * (257 + sysP); };
 	bool wide_again = false;
-	for (int32_t pair : pairs) wide_again |= (b->h_flags[pair] & 16) != 0;
+	for (int32_t pair : pairs) wide_again |= (b->h_flags[pair] & FLAG_COOP_WIDE) != 0;
 	// (first-pass window: a fifth of tl+ql — or, where the batch's divergence is known, 6.5 d (tl+ql): 50 kb pairs at 15 % outgrew the 64-column slots and ran twice)
 	const int64_t est1 = std::min<int64_t>(len + 1, std::max<int64_t>(8192, b->div_est > 0 && g->div_aware ? (int64_t)(6.5 * b->div_est * (double)len) : len / 5));
 	const int64_t est2 = std::min<int64_t>(len + 1, 2 * ((int64_t)opt.step + 2 * P.nH) + 8);
@@ -496,12 +504,8 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 		const int64_t budget = g->lowmem_budget_mb > 0 ? g->lowmem_budget_mb << 20 : (int64_t)8 << 30;
 		two_pass = std::max<int64_t>((int64_t)1 << 30, 6000 * len) * (int64_t)NG * g->coop_tb_mult * (c_first == 1 ? 12 : 9) / 8 > budget;
 	}
-	// granules crossing waves: [nH][TC][2 sides][4] x 8 bytes (twice for the two-pass mode: values and their provenance);
-	// misc: flags, barrier words, pass state, then the flag ring
-	const size_t gran_bytes = 4096; // (the per-penalty granule exchange of mwf_coop.hip is gone: the field remains for the layout of the misc block)
-	const size_t flag_ring_bytes = 0; // (the flag ring of the removed per-penalty hand-off kernel)
-	const size_t misc_bytes = 4096 + flag_ring_bytes;
-	if (ensure(g, g->coop_edge, NG * gran_bytes)) return -1;
+	// misc, per group: flags | +1024 barrier words | +2048 pass state
+	const size_t misc_bytes = 4096;
 	if (ensure(g, g->coop_misc, NG * misc_bytes + 4096)) return -1; // (+ the pair ids behind the last group)
 	int64_t rows_slot = 0, tb_bytes = 0, cig_scratch = 0, seg_slot = 0;
 	if (cigar) {
@@ -521,8 +525,8 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 		const int64_t lay = (two_pass ? c_second : c_first) == 1 ? 12 : (two_pass ? c_second : c_first) == 2 ? 10 : 9; // the pass whose traceback sets the size: 64-column slots own 48 (4/3 of the exact rows), 256-column ones 240 (the second pass of the low-memory mode is narrow: it fits whatever the first needed)
 		// (+ a few slots of margin per epoch of 256 penalties; epochs by the guessed penalty, not by the worst case — 10 M penalties for the 5 Mb pair, 20 GB of margin)
 		const int64_t ep_guess = (len * 3 / 100 + 1024) / 256 + 2;
-		if (use_sys) guess = std::min<int64_t>(g->coop_tb_cap, guess / 8 * lay + ep_guess * 8 * 65536 * (int64_t)NG);
-		int64_t want = std::min(use_sys ? worst / 8 * lay + (rows_slot / 256 + 2) * 8 * 65536 * (int64_t)NG : worst, g->tb_budget_mb > 0 ? (g->tb_budget_mb << 20) : guess * g->coop_tb_mult);
+		guess = std::min<int64_t>(g->coop_tb_cap, guess / 8 * lay + ep_guess * 8 * 65536 * (int64_t)NG);
+		int64_t want = std::min(worst / 8 * lay + (rows_slot / 256 + 2) * 8 * 65536 * (int64_t)NG, g->tb_budget_mb > 0 ? (g->tb_budget_mb << 20) : guess * g->coop_tb_mult);
 		if ((int64_t)g->tb.bytes >= want) want = (int64_t)g->tb.bytes;
 		else {
 			size_t fr = 0, tot = 0;
@@ -562,15 +566,13 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	const int64_t sys_rows = std::max(bound, bound1) + 2, sys_log_ints = 2 * (sys_rows + 256 + 8), sys_ep_words = 2 * (sys_rows / 256 + 3);
 	const int sys_nef = 2 * P.e1 + 2 * P.e2; // E/F register arrays per column: what a lane publishes and parks besides its H rows
 	const int64_t sys_box_group = TC * 2 * std::max(sys_box_ints(sysP, sys_nef, two_pass), sys_box_ints(sysP2, sys_nef, false)), sys_park_group = TC * sys_park_ints(sys_nef, two_pass);
-	if (use_sys) {
-		if (ensure(g, g->sys_ring, NG * (size_t)TC * P.nH * 256 * 4)) return -1;
-		if (ensure(g, g->sys_good, NG * (size_t)P.nH * TC * 4 * 8)) return -1;
-		if (ensure(g, g->sys_box, NG * (size_t)sys_box_group * 4)) return -1;
-		if (ensure(g, g->sys_prog, NG * (size_t)TC * 64)) return -1;
-		if (ensure(g, g->sys_log, NG * (size_t)sys_log_ints * 4)) return -1;
-		if (ensure(g, g->sys_ep, NG * (size_t)sys_ep_words * 8)) return -1;
-		if (ensure(g, g->sys_park, NG * (size_t)sys_park_group * 4)) return -1;
-	}
+	if (ensure(g, g->sys_ring, NG * (size_t)TC * P.nH * 256 * 4)) return -1;
+	if (ensure(g, g->sys_good, NG * (size_t)P.nH * TC * 4 * 8)) return -1;
+	if (ensure(g, g->sys_box, NG * (size_t)sys_box_group * 4)) return -1;
+	if (ensure(g, g->sys_prog, NG * (size_t)TC * 64)) return -1;
+	if (ensure(g, g->sys_log, NG * (size_t)sys_log_ints * 4)) return -1;
+	if (ensure(g, g->sys_ep, NG * (size_t)sys_ep_words * 8)) return -1;
+	if (ensure(g, g->sys_park, NG * (size_t)sys_park_group * 4)) return -1;
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
 	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
@@ -597,9 +599,9 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	a.coop_pair = pairs[0];
 	a.coop_spin_limit = (uint32_t)g->coop_spin_limit;
 	a.coop_groups = n_groups, a.coop_group_size = Gs;
-	a.coop_edge = (int32_t*)g->coop_edge.p, a.coop_edge_stride = (int64_t)(gran_bytes / 4);
-	a.coop_sedge_off = two_pass ? (int64_t)(gran_bytes / 8) : 0;
-	a.coop_flags = (int32_t*)g->coop_misc.p, a.coop_misc_stride = (int64_t)misc_bytes; // per group: flags | +1024 barrier words | +2048 pass state | +4096 flag ring
+	// (the granule fields of BatchArgs — the edge array, its stride, the provenance offset — belonged to the removed per-penalty hand-off kernel and no device code reads them:
+	// they stay zero from the memset, and leave BatchArgs with the next change that touches the kernels — mwf_internal.h is part of every kernel's fingerprint)
+	a.coop_flags = (int32_t*)g->coop_misc.p, a.coop_misc_stride = (int64_t)misc_bytes;
 	a.coop_sync = (unsigned int*)((char*)g->coop_misc.p + 1024);
 	a.coop_state = (int32_t*)((char*)g->coop_misc.p + 2048);
 	int32_t *d_ids = (int32_t*)((char*)g->coop_misc.p + NG * misc_bytes);
@@ -608,18 +610,16 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 
 	// the same launch on the systolic kernel: a private H ring per chunk slot, its own good-bit rows, hand-off boxes, edge log
 	BatchArgs as = a;
-	if (use_sys) {
-		as.ring = (int32_t*)g->sys_ring.p, as.good = (unsigned long long*)g->sys_good.p; // (sized for four columns per lane)
-		as.rows_slot = sys_rows;
-		as.sys_p = sysP;
-		as.sys_coop_launch = 1;
-		as.sys_spread = 1; // consecutive chunks on consecutive workgroups: 763 against 787 ms on the 5 Mb pair, 63.5 against 65.0 on the 150 kb pair
-		as.sys_box = (int32_t*)g->sys_box.p, as.sys_box_stride = sys_box_group;
-		as.sys_prog = (unsigned long long*)g->sys_prog.p, as.sys_prog_stride = TC * 8;
-		as.sys_log = (int32_t*)g->sys_log.p, as.sys_log_stride = sys_log_ints;
-		as.sys_ep = cigar ? (int64_t*)g->sys_ep.p : nullptr, as.sys_ep_stride = sys_ep_words;
-		as.sys_park = (int32_t*)g->sys_park.p, as.sys_park_stride = sys_park_group;
-	}
+	as.ring = (int32_t*)g->sys_ring.p, as.good = (unsigned long long*)g->sys_good.p; // (sized for four columns per lane)
+	as.rows_slot = sys_rows;
+	as.sys_p = sysP;
+	as.sys_coop_launch = 1;
+	as.sys_spread = 1; // consecutive chunks on consecutive workgroups: 763 against 787 ms on the 5 Mb pair, 63.5 against 65.0 on the 150 kb pair
+	as.sys_box = (int32_t*)g->sys_box.p, as.sys_box_stride = sys_box_group;
+	as.sys_prog = (unsigned long long*)g->sys_prog.p, as.sys_prog_stride = TC * 8;
+	as.sys_log = (int32_t*)g->sys_log.p, as.sys_log_stride = sys_log_ints;
+	as.sys_ep = cigar ? (int64_t*)g->sys_ep.p : nullptr, as.sys_ep_stride = sys_ep_words;
+	as.sys_park = (int32_t*)g->sys_park.p, as.sys_park_stride = sys_park_group;
 	auto reset_sys = [&](bool all) -> int { // counters at zero, nothing published
 		for (size_t q = 0; q < NG; ++q) {
 			char *m = (char*)g->coop_misc.p + q * misc_bytes;
@@ -657,7 +657,7 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	}
 	g->stats.grid = Gs * n_groups, g->stats.block = 512, g->stats.kernel_kind = 1;
 	b->last_grid = std::max(b->last_grid, Gs * n_groups);
-	for (int32_t pair : pairs) b->h_kind[pair] = 1, b->h_flags[pair] = (int8_t)((b->h_flags[pair] & ~(2 | 32)) | (n_groups > 1 ? 2 : 0) | ((c_first == 1 || (low_mem && c_second == 1)) ? 32 : 0));
+	for (int32_t pair : pairs) b->h_kind[pair] = 1, b->h_flags[pair] = (int8_t)((b->h_flags[pair] & ~(FLAG_COOP_SHARED | FLAG_COOP_NARROW)) | (n_groups > 1 ? FLAG_COOP_SHARED : 0) | ((c_first == 1 || (low_mem && c_second == 1)) ? FLAG_COOP_NARROW : 0));
 	HIP_TRY(g, hipStreamSynchronize(g->stream)); // the device stays ours until the kernels are through
 	return 0;
 }
@@ -677,6 +677,334 @@ bool coop_can_grow(mwf_gpu_t *g)
 	return (int64_t)(fr / 10 * 9) > (int64_t)g->tb.bytes / 2; // room for at least half as much again
 }
 
+// ---- one align call, step by step ------------------------------------------------------------------------------------------
+
+// Where the result arrays lie.  A small score-only batch (the single pair of a drop-in call) gets them in a page of pinned host
+// memory that the kernels write directly: results() then waits for the stream and reads them — no copy to enqueue and wait
+// for (a 200 bp call: ~8 us).  The CIGAR counter is device-side atomics: CIGAR-mode batches keep everything in the block.
+static int place_results(mwf_gpu_t *g, mwf_gpu_batch_t *b, bool cigar)
+{
+	const BlockLayout L = layout_block((size_t)b->n, 0, false); // (only differences between result offsets are used)
+	bool pin = g->res_pin_on && !cigar && b->n <= 64 && L.out_end - L.head <= 4096 && (g->res_pin_owner == nullptr || g->res_pin_owner == b);
+	if (pin && !g->res_pin && hipHostMalloc(&g->res_pin, 4096, hipHostMallocDefault) != hipSuccess) (void)hipGetLastError(), g->res_pin = nullptr, pin = false;
+	if (pin != b->out_in_pin || (pin && g->res_pin_owner != b)) {
+		if (b->busy) HIP_TRY(g, hipStreamSynchronize(g->stream)); // an align nobody waited for still writes the old arrays
+		char *base = pin ? (char*)g->res_pin - L.head : (char*)b->block.p + (b->out_off - L.head);
+		b->d_status = (int32_t*)(base + L.status), b->d_s = (int32_t*)(base + L.s), b->d_ncig = (int32_t*)(base + L.ncig);
+		b->d_iter = (int64_t*)(base + L.iter), b->d_cigoff = (int64_t*)(base + L.cigoff), b->d_cells1 = (int64_t*)(base + L.cells1);
+		if (g->res_pin_owner == b && !pin) g->res_pin_owner = nullptr;
+		if (pin) g->res_pin_owner = b;
+		b->out_in_pin = pin;
+	}
+	if (cigar && !b->d_cig_pool) {
+		if (take_block(g, g->spare_cig, b->cig, (size_t)b->cig_pool_words * 4)) return -1;
+		b->d_cig_pool = (uint32_t*)b->cig.p;
+	}
+	return 0;
+}
+
+// The plan of the last align applies when nothing it was derived from changed: the options that classify pairs and the tunables.  Leaves the batch's
+// longest pair and largest penalty bound in the cache either way.
+static void revalidate_plan(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const Penalty &P0)
+{
+	mwf_gpu_batch_t::PlanCache &PC = b->plan;
+	const int32_t ok[8] = {opt.flag & MWF_F_CIGAR, opt.x, opt.o1, opt.e1, opt.o2, opt.e2, opt.step, opt.max_s};
+	// the tunables as a generation count (every mwf_gpu_set() bumps it) + the engine the plan was made on + the traced pair
+	const int64_t tk[3] = {g->tun_gen, (int64_t)(intptr_t)g, b->debug_pair};
+	if (PC.valid && (memcmp(ok, PC.opt_key, sizeof(ok)) || memcmp(tk, PC.tun_key, sizeof(tk)))) PC.valid = false;
+	if (!PC.valid) memcpy(PC.opt_key, ok, sizeof(ok)), memcpy(PC.tun_key, tk, sizeof(tk)), PC.has_groups = false, PC.wide_state = 0;
+	if (PC.valid) return;
+	int64_t max_len = 0, max_bound = 0;
+	for (int32_t i = 0; i < b->n; ++i) {
+		max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+		max_bound = std::max(max_bound, penalty_bound(P0, opt.max_s, b->h_tl[i], b->h_ql[i], true));
+	}
+	PC.max_len = max_len, PC.max_bound = max_bound, PC.valid = true;
+}
+
+// Every pair "not run", CIGAR pool and work counters at zero: one small kernel — unless the result arrays can be written from here
+// (the pinned result page of a small score-only batch: the single pair of a drop-in call) or came up initialised with the batch
+// (a small batch's first align); the kernels of such a call then run without a work counter where they can (run_batch_kernel).
+// preset: no reset kernel ran.
+static int reset_results(mwf_gpu_t *g, mwf_gpu_batch_t *b, bool was_busy, bool &preset)
+{
+	g->queue_next = 0, g->lane_set_next = 0;
+	preset = false;
+	if (b->out_in_pin && !was_busy) {
+		for (int32_t i = 0; i < b->n; ++i) b->d_status[i] = -1, b->d_s[i] = -2;
+		preset = true;
+	} else if (b->results_preinit) preset = true;
+	b->results_preinit = false;
+	g->queue_clean = !preset;
+	b->cig_block_left = kCigBlockGrid;
+	if (!preset && launch_reset(b->d_status, b->d_s, b->n, b->d_cig_head, (int32_t*)g->queue.p, kQueueInts, g->stream)) { g->err = "kernel launch failed (reset)"; return -1; }
+	std::fill(b->h_flags.begin(), b->h_flags.end(), 0);
+	return 0;
+}
+
+// A few long pairs: each one gets the whole device in turn.  taken: the batch ran here.
+static int route_whole_device(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const Penalty &P0, int64_t max_len, bool &taken)
+{
+	taken = false;
+	// (round 3: from 20 000 bases of target + query on, a batch of up to sixteen pairs is faster on the whole-device kernel than one
+	// workgroup per pair on any other — 1 x 12 kb 4.1 against 6.4 ms, 16 x 25 kb 11.5 / 20.5, 1 x 32 kb 9.6 / 26.1, a single 10 kb pair
+	// 3.4 against 5.8 ms on the packed band kernel; profiles/r03/few_long_pairs.txt)
+	// (with traceback already from 15 000 on: 1 x 10 kb 5.1 against 7.2 ms on the packed band kernel, 16 x 8 kb 5.2 / 6.2)
+	const int64_t coop_len = g->coop_min_len > 0 ? g->coop_min_len : ((opt.flag & MWF_F_CIGAR) ? 15000 : 20000);
+	// The whole-device kernel takes time ~ (tl+ql) per round of pairs side by side (each on its own group of workgroups); the generic kernel
+	// runs up to 256 (512) pairs at once in time ~ (tl+ql)^2.  Measured at 3 % divergence (profiles/few_long_pairs.py, round 3): 50 kb pairs
+	// 22 ms per round of 16 against 60 ms for any number of them on the generic kernel, 100 kb pairs 44 ms per round of 8 against 245 ms,
+	// 150 kb pairs 68 ms against 545 ms — the whole-device kernel wins while the batch needs fewer than about 2.7 (tl+ql)/100 000 rounds.
+	bool coop = g->force_kind == 1;
+	int n_cu_coop = 0;
+	if (coop || (g->force_kind < 0 && max_len >= coop_len && coop_supported(P0))) {
+		n_cu_coop = coop_grid_limit(g);
+		const int coop_side_by_side = n_cu_coop > 0 ? std::max(1, n_cu_coop / coop_group_size(n_cu_coop, max_len, false, sys_owned_cols(g->sys_p, 4))) : 1;
+		// (low-memory mode: the alternative is the generic kernel's two-pass form, three times its high-memory time — 17 x 30 kb @ 5 % 186 ms against 50 ms per round of
+		// sixteen here, 48 x 100 kb @ 3 % 694 ms against 555 ms in six rounds of eight: at least four rounds, where the rule above allowed one round of 30 kb pairs;
+		// profiles/r06/routing_survey_long_before.txt, _after.txt)
+		const bool lowmem_call = (opt.flag & MWF_F_CIGAR) && opt.step > 0;
+		const int64_t coop_rounds = lowmem_call ? std::max<int64_t>(4, max_len * 32 / 1000000) : std::max<int64_t>(1, max_len * 27 / 1000000);
+		int64_t coop_max_pairs = std::max<int64_t>(1, std::min<int64_t>(256, coop_rounds * coop_side_by_side));
+		if (max_len < 65536) coop_max_pairs = std::min<int64_t>(coop_max_pairs, lowmem_call ? 48 : 16); // (measured up to sixteen)
+		coop = coop || b->n <= coop_max_pairs;
+	}
+	if (!coop) return 0;
+	if (!coop_supported(P0)) { g->err = "whole-device kernel does not support these penalties"; return -2; }
+	if (n_cu_coop < 1) { g->err = "whole-device kernel cannot be made resident"; return -1; }
+	std::vector<int32_t> idx(b->h_order.begin(), b->h_order.end());
+	std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; }); // longest first
+	for (size_t at = 0; at < idx.size();) {
+		const int64_t len0 = (int64_t)b->h_tl[idx[at]] + b->h_ql[idx[at]];
+		const int Gs = coop_group_size(n_cu_coop, len0, false, sys_owned_cols(g->sys_p, 4));
+		const size_t n_side = std::min<size_t>(idx.size() - at, (size_t)std::max(1, n_cu_coop / Gs));
+		const bool last = at + n_side == idx.size();
+		if (n_side <= 1 || b->debug_pair >= 0) { // alone (also: band traces are single-pair diagnostics)
+			if (run_coop_pair(g, b, opt, idx[at], at == 0, at + 1 == idx.size())) return -1;
+			at += 1;
+			continue;
+		}
+		if (run_coop_group(g, b, opt, std::vector<int32_t>(idx.begin() + at, idx.begin() + at + n_side), Gs, at == 0, last)) return -1;
+		at += n_side;
+	}
+	taken = true;
+	return 0;
+}
+
+// what the class rule depends on (mwf_plan_classes.h), from the engine, the batch and the call's options
+static ClassRule make_rule(const mwf_gpu_t *g, const mwf_gpu_batch_t *b, const mwf_opt_t &opt, const Penalty &P0)
+{
+	ClassRule R;
+	R.pen = P0, R.max_s = opt.max_s, R.step = opt.step, R.low_mem = (opt.flag & MWF_F_CIGAR) && opt.step > 0;
+	R.band2_ok = band2_supported(P0), R.lane_ok = lane_supported(P0), R.mid_ok_pen = mid_supported(P0), R.biased512_ok = band2_biased512_supported(P0), R.nib_ok = band2_nib_supported(P0);
+	R.biased512_chunks = band2_biased512_chunks(), R.span_chunks = band2_span_chunks(), R.mid_lds_bytes = mid_lds_bytes;
+	R.force_kind = g->force_kind, R.block = g->block, R.band_pack = g->band_pack, R.band_span = g->band_span, R.seq2bit = g->seq2bit, R.wide_slots = g->wide_slots, R.alpha16 = g->alpha16;
+	R.lane_max_len = g->lane_max_len, R.mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
+	R.div_aware = g->div_aware, R.div_est = b->div_est, R.know_acgt = !b->h_acgt.empty() && g->seq2bit != 0, R.alpha_active = b->alpha_active;
+	R.finish();
+	return R;
+}
+
+static int pair_alpha(const mwf_gpu_batch_t *b, int32_t i) { return (size_t)i < b->h_alpha.size() ? b->h_alpha[(size_t)i] : -1; }
+
+struct ClassPlan {
+	GroupInfo gi[kNumClasses];
+	bool mid_bytes = false;
+};
+
+struct PairInfo { int64_t bound, bound1, exp_win; }; // what the rule worked out for a pair besides its class: the maxima of its group are made of these
+
+// the maxima of every class's group (a function of its own: inlined behind the per-pair rule the loop ran at half its speed, profiles/plan_refactor/plan_timing.txt)
+#if defined(__GNUC__)
+__attribute__((noinline))
+#endif
+static void group_maxima(const mwf_gpu_batch_t *b, const std::vector<int8_t> &cls, const std::vector<PairInfo> &info, double div_r, ClassPlan &cp)
+{
+	for (int32_t i = 0; i < b->n; ++i) {
+		const int64_t tl = b->h_tl[i], ql = b->h_ql[i], len = tl + ql;
+		const int c = cls[(size_t)i];
+		const PairInfo &pi = info[(size_t)i];
+		GroupInfo &G = cp.gi[c];
+		++G.n;
+		G.max_len = std::max(G.max_len, len), G.max_bound = std::max(G.max_bound, pi.bound);
+		G.max_bound1 = std::max(G.max_bound1, pi.bound1);
+		// (the mid class: the window its pairs are expected to reach, forced gap included — its launch picks the workgroup size by it)
+		const int64_t exp_win = row(c).geom == GEOM_MID ? std::min<int64_t>(len + 1, (int64_t)((double)len * div_r * 0.28) + 2 * std::abs(tl - ql)) : pi.exp_win;
+		G.max_tl = std::max<int64_t>(G.max_tl, tl), G.max_exp_win = std::max(G.max_exp_win, exp_win);
+		G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, ((tl + 3) & ~3LL) + 8 + ((ql + 3) & ~3LL) + 16);
+	}
+}
+
+// Class of every pair (cls; b->h_class and b->h_flags get fallback and flags) and the maxima of every class's group.
+static void classify_and_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const ClassRule &rule, std::vector<int8_t> &cls, ClassPlan &cp)
+{
+	// (a copy of its own: the per-pair loop stores bytes — h_class, h_flags, cls —, which may alias anything reached through a reference, and the rule's
+	// fields would be read again for every pair; profiles/plan_refactor/plan_timing.txt)
+	ClassRule R = rule;
+	const bool mid_ok = R.mid_batch && b->n <= R.mid_cap;
+	// A batch of reads whose lengths straddle the limit is not split for a few pairs: where most of the pairs up to 10 % beyond the limit lie below it, the rest follow
+	// them (2000 x 300 bp with 28 pairs beyond: 0.37 ms as one lane launch, 0.50 with a launch of their own)
+	int64_t lane_limit = mid_ok ? std::min(g->lane_max_len, 320) : g->lane_max_len;
+	if (R.lane_on && !mid_ok && (R.classes || R.small_only)) {
+		int64_t n_lo = 0, n_hi = 0;
+		for (int32_t i = 0; i < b->n; ++i) {
+			const int64_t w = (int64_t)((double)std::max(b->h_tl[i], b->h_ql[i]) * R.div_lane);
+			if (std::abs(b->h_tl[i] - b->h_ql[i]) > 24) continue;
+			n_lo += w <= lane_limit, n_hi += w > lane_limit && w <= lane_limit * 11 / 10;
+		}
+		if (n_hi > 0 && n_lo >= n_hi) lane_limit = lane_limit * 11 / 10;
+	}
+	R.lane_limit = lane_limit;
+	std::vector<PairInfo> info((size_t)b->n);
+	std::vector<int8_t> mid_cand;   // large batches: pairs the mid kernel would take if they are few
+	int32_t n_cand = 0;
+	if (R.mid_batch && !mid_ok) mid_cand.assign((size_t)b->n, 0);
+	// (inlined at both of its uses, like the rule itself: as a call through the closure it costs the first align of a 40 000 x 150 bp batch 0.07 ms)
+	auto classify = [&](int32_t i, bool allow_mid) __attribute__((always_inline)) {
+		const PairPlan pp = classify_pair(R, b->h_tl[i], b->h_ql[i], R.know_acgt ? b->h_acgt[i] != 0 : true, pair_alpha(b, i), allow_mid);
+		info[(size_t)i] = PairInfo{pp.bound, pp.bound1, pp.exp_win};
+		b->h_class[i] = pp.fallback, b->h_flags[i] = pp.flags;
+		if (pp.mid_candidate && !mid_cand.empty() && !mid_cand[(size_t)i]) mid_cand[(size_t)i] = 1, ++n_cand;
+		cp.mid_bytes |= pp.mid_bytes;
+		cls[(size_t)i] = pp.cls;
+	};
+	for (int32_t i = 0; i < b->n; ++i) classify(i, mid_ok);
+	if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] classes of %d pairs: divergence estimate %.4f (weight %.2f)\n", b->n, (double)b->div_est, R.div_r);
+	if (n_cand > 0 && n_cand <= R.mid_cap)
+		for (int32_t i = 0; i < b->n; ++i)
+			if (mid_cand[(size_t)i]) classify(i, true);
+	group_maxima(b, cls, info, R.div_r, cp);
+}
+
+// The processing order: groups in run order, longest first inside a group (the persistent workgroups finish together; the classes on the shared
+// work counter then by predicted work, below).  b->h_len_order is sorted longest first and that order is stable: one pass over it deals the pairs to their groups.
+static int order_pairs(mwf_gpu_t *g, mwf_gpu_batch_t *b, const std::vector<int8_t> &cls, const ClassPlan &cp)
+{
+	int32_t start[kNumClasses], end[kNumClasses]; // every class's stretch of the order
+	std::vector<int32_t> order((size_t)b->n);
+	{
+		int32_t at = 0;
+		for (PairClass c : kRunOrder) start[c] = at, at += cp.gi[c].n, end[c] = at;
+	}
+	if (b->h_len_order.empty()) {
+		b->h_len_order.resize((size_t)b->n);
+		std::iota(b->h_len_order.begin(), b->h_len_order.end(), 0);
+		std::stable_sort(b->h_len_order.begin(), b->h_len_order.end(), [&](int32_t x, int32_t y) {
+			return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y];
+		});
+	}
+	{
+		int32_t next[kNumClasses];
+		std::copy(start, start + kNumClasses, next);
+		for (int32_t i : b->h_len_order) order[(size_t)next[cls[i]]++] = i;
+	}
+	// The classes on the shared work counter — the 512-thread geometries (wide, its biased, 4-bit and byte-wise copies) and the 1024-thread span
+	// geometry (ClassRow::by_work) — are dealt by predicted WORK, largest first: in an equal-length batch "longest first" says nothing about how long a pair takes.
+	// 1024 x 10 kb at 5 %: s 2118 ... 2838 (sd 118) on one length; the pairs dealt last finished far apart while CUs idled (the drain).
+	// The estimate: s ~ (tl + ql) x d, d from the share of the query's 8-mers found in the target over the WHOLE pair (correlation 0.88 with s;
+	// the batch sketch's 1500-base prefix 0.34).  A class that fits on the device at once (no more pairs than workgroups) has nothing to deal.
+	auto dealt = [&](PairClass c) { return row(c).by_work && cp.gi[c].n > 2 * g->n_cu; }; // (two workgroups per CU on the 512-thread geometries; the span geometry holds fewer)
+	bool reorder = false;
+	for (PairClass c : kRunOrder) reorder |= dealt(c);
+	if (reorder && g->work_order != 0 && (g->work_order != 2 || (int32_t)b->h_iter.size() == b->n)) {
+		const int32_t lo = start[kRunOrder[by_work_first()]], hi = end[kRunOrder[by_work_end() - 1]]; // (kRunOrder keeps them side by side)
+		std::vector<double> key((size_t)b->n, 0.0);
+		if (g->work_order == 1) {
+			// one workgroup per pair reads both sequences from the device (at align: the caller's arrays need only be valid then); the pair ids go up in
+			// the order array, which gets the final order below
+			if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{order.data() + lo, (size_t)(hi - lo) * 4}})) return -1;
+			b->h_order.clear();
+			if (launch_pair_sketch(b->d_seqs, b->alpha_active ? b->d_rt_off : b->d_t_off, b->d_tl, b->alpha_active ? b->d_rq_off : b->d_q_off, b->d_ql, b->d_order, hi - lo, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
+			std::vector<int32_t> hits((size_t)(hi - lo));
+			HIP_TRY(g, hipMemcpyAsync(hits.data(), b->d_dbg4, hits.size() * 4, hipMemcpyDeviceToHost, g->stream)); // (scratch behind the results: written by this align's kernels only with MWF_F_DEBUG)
+			HIP_TRY(g, hipStreamSynchronize(g->stream));
+			for (int32_t k = lo; k < hi; ++k) {
+				const int32_t i = order[(size_t)k], tl = b->h_tl[i], ql = b->h_ql[i];
+				key[(size_t)i] = (double)((int64_t)tl + ql) * sketch_divergence(hits[(size_t)(k - lo)], std::max(ql - 7, 0), tl);
+			}
+		} else if (g->work_order == 2) {
+			for (int32_t k = lo; k < hi; ++k) key[(size_t)order[(size_t)k]] = (double)b->h_iter[(size_t)order[(size_t)k]];
+		}
+		for (PairClass c : kRunOrder) {
+			if (!dealt(c)) continue;
+			const auto first = order.begin() + start[c], last = order.begin() + end[c];
+			if (g->work_order == 3) std::reverse(first, last); // (shortest first: the other bound of the measurement)
+			else std::sort(first, last, [&](int32_t x, int32_t y) {
+				if (key[(size_t)x] != key[(size_t)y]) return key[(size_t)x] > key[(size_t)y];
+				const int64_t lx = (int64_t)b->h_tl[x] + b->h_ql[x], ly = (int64_t)b->h_tl[y] + b->h_ql[y];
+				return lx != ly ? lx > ly : x < y;
+			});
+		}
+	}
+	if (order != b->h_order) {
+		b->h_order.swap(order);
+		if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{b->h_order.data(), b->h_order.size() * 4}})) return -1; // (waits for earlier work on the stream first)
+	}
+	return 0;
+}
+
+// One launch per class that has pairs, in run order; everything a launch asks for comes from the class's row of kClassTable.
+static int launch_classes(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const ClassRule &R, const ClassPlan &cp, bool preset)
+{
+	mwf_gpu_batch_t::PlanCache &PC = b->plan;
+	int n_groups = 0, done_groups = 0;
+	for (const GroupInfo &G : cp.gi) n_groups += G.n > 0;
+	mwf_opt_t opt_hi = opt;
+	opt_hi.step = 0;
+	size_t at = 0;
+	for (PairClass c : kRunOrder) {
+		const GroupInfo &G = cp.gi[c];
+		const ClassRow &T = row(c);
+		if (G.n == 0) continue;
+		++done_groups;
+		// (the lane class of a batch of reads hands its overflows to a follow-up launch on the device, below)
+		const bool lane_retry = T.retry_slot >= 0 && g->dev_retry && G.n >= 1024 && !preset && g->force_kind < 0 && g->block == 0 && R.mid_ok_pen && G.max_len <= 1200 &&
+		                        G.max_tl + G.max_bound < 32760 && !R.low_mem;
+		// (a forced kernel or block keeps the batch in one group: the 4-bit form then only where every pair of it is class 3)
+		bool all_nib = !R.classes && c == CLS_GENERIC && g->force_kind != 0;
+		for (int32_t i = 0; all_nib && i < b->n; ++i) all_nib = R.nib_pair(pair_alpha(b, i));
+		// the 512-thread geometry of three or four slots: four when asked for, or until an align has shown that three hold every pair (then the kernel reports)
+		const bool four_slots = T.wide && (g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean));
+		LaunchReq rq;
+		rq.opt = c == CLS_LOWMEM ? opt : opt_hi;
+		rq.d_order = b->d_order + at, rq.n_items = G.n, rq.group = G;
+		rq.geom = T.geom;
+		rq.copy = all_nib ? COPY_NIB : (T.geom == GEOM_MID && cp.mid_bytes) ? COPY_BYTES : T.copy;
+		rq.want_kind = (R.classes || T.geom == GEOM_LANE || T.geom == GEOM_MID) ? T.want_kind : -1; // (without classes only the lane and mid kernels' groups name their kernel)
+		rq.window_hint = four_slots ? kBandWide4Window : (T.geom == GEOM_BIASED || T.geom == GEOM_MID) ? G.max_exp_win : 0;
+		rq.report_wide = four_slots;
+		rq.retry_list = lane_retry ? 1 : 0, rq.retry_slot = lane_retry ? T.retry_slot : 0;
+		rq.timed_begin = done_groups == 1, rq.timed_end = !lane_retry && done_groups == n_groups;
+		int ran = 0;
+		const int rc = run_batch_kernel(g, b, rq, &ran);
+		if (T.wide && g->wide_slots == 0 && PC.wide_state == 0 && g->queue_clean && ran == 2 && g->stats.block == 512) PC.wide_measured = true;
+		// Batches of reads: what the lane kernel hands back (a window that left its chunks: one read in tens of thousands) is re-run by a follow-up launch of
+		// the mid kernel, whose span holds the widest window such a pair can have — from a list the lane kernel filled ON THE DEVICE.  Round 4 read the status
+		// words back, launched, waited and read them again: ~0.2 ms behind a 0.5 ms launch.  (An empty list costs the launch of a few idle workgroups.)
+		if (rc == 0 && lane_retry) {
+			const mwf_gpu_stats_t keep = g->stats;
+			// (every entry of the list — the mid kernel strides over it by its grid —, on at most 32 workgroups: an empty list costs the launch of a few idle ones)
+			LaunchReq r2;
+			r2.opt = opt_hi, r2.d_order = b->d_retry_ids + T.retry_slot * kRetryCap, r2.n_items = kRetryCap, r2.slots = 32, r2.group = G;
+			r2.geom = GEOM_MID, r2.copy = T.copy, r2.want_kind = 2, r2.retry_list = 2, r2.retry_slot = T.retry_slot, r2.timed_end = done_groups == n_groups;
+			int ran2 = 0;
+			const int rc2 = run_batch_kernel(g, b, r2, &ran2);
+			const int32_t launches = g->stats.n_launches;
+			g->stats = keep, g->stats.n_launches = launches; // (the statistics describe the class's own launch)
+			if (rc2) return -1;
+			b->dev_retry_used = true;
+		}
+		if (rc) return -1;
+		const bool three_slots = T.wide && ran == 2 && g->stats.block == 512 && !four_slots;
+		for (size_t j = at; j < at + (size_t)G.n; ++j) {
+			const int32_t i = b->h_order[j];
+			b->h_kind[i] = (int8_t)ran, b->h_flags[i] = (int8_t)((b->h_flags[i] & ~FLAG_THREE_SLOTS) | (three_slots ? FLAG_THREE_SLOTS : 0));
+		}
+		at += (size_t)G.n;
+	}
+	return 0;
+}
+
 } // namespace host
 } // namespace mwf
 
@@ -694,402 +1022,33 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	g->stats = mwf_gpu_stats_t{};
 	if (b->n == 0) { b->aligned = b->finalized = true, b->alpha_known = g->alpha_remap != 0; return 0; } // (an empty batch: nothing to classify or copy, and with "alpha_remap" 1 its zero classes are known)
 	if (alpha_prepare(g, b)) return -1; // ("alpha_remap": classes and copies first — the plan below follows them)
-	const bool cigar = (opt->flag & MWF_F_CIGAR) != 0;
-	{ // Where the result arrays lie.  A small score-only batch (the single pair of a drop-in call) gets them in a page of pinned host
-	  // memory that the kernels write directly: results() then waits for the stream and reads them — no copy to enqueue and wait
-	  // for (a 200 bp call: ~8 us).  The CIGAR counter is device-side atomics: CIGAR-mode batches keep everything in the block.
-		const BlockLayout L = layout_block((size_t)b->n, 0, false); // (only differences between result offsets are used)
-		bool pin = g->res_pin_on && !cigar && b->n <= 64 && L.out_end - L.head <= 4096 && (g->res_pin_owner == nullptr || g->res_pin_owner == b);
-		if (pin && !g->res_pin && hipHostMalloc(&g->res_pin, 4096, hipHostMallocDefault) != hipSuccess) (void)hipGetLastError(), g->res_pin = nullptr, pin = false;
-		if (pin != b->out_in_pin || (pin && g->res_pin_owner != b)) {
-			if (b->busy) HIP_TRY(g, hipStreamSynchronize(g->stream)); // an align nobody waited for still writes the old arrays
-			char *base = pin ? (char*)g->res_pin - L.head : (char*)b->block.p + (b->out_off - L.head);
-			b->d_status = (int32_t*)(base + L.status), b->d_s = (int32_t*)(base + L.s), b->d_ncig = (int32_t*)(base + L.ncig);
-			b->d_iter = (int64_t*)(base + L.iter), b->d_cigoff = (int64_t*)(base + L.cigoff), b->d_cells1 = (int64_t*)(base + L.cells1);
-			if (g->res_pin_owner == b && !pin) g->res_pin_owner = nullptr;
-			if (pin) g->res_pin_owner = b;
-			b->out_in_pin = pin;
-		}
-	}
-	if (cigar && !b->d_cig_pool) {
-		if (take_block(g, g->spare_cig, b->cig, (size_t)b->cig_pool_words * 4)) return -1;
-		b->d_cig_pool = (uint32_t*)b->cig.p;
-	}
-	// the plan of the last align applies when nothing it was derived from changed: the options that classify pairs and the tunables
+	if (place_results(g, b, (opt->flag & MWF_F_CIGAR) != 0)) return -1;
+	const Penalty P0 = make_penalty(*opt);
 	mwf_gpu_batch_t::PlanCache &PC = b->plan;
-	{
-		const int32_t ok[8] = {opt->flag & MWF_F_CIGAR, opt->x, opt->o1, opt->e1, opt->o2, opt->e2, opt->step, opt->max_s};
-		// the tunables as a generation count (every mwf_gpu_set() bumps it) + the engine the plan was made on + the traced pair
-		const int64_t tk[14] = {g->tun_gen, (int64_t)(intptr_t)g, b->debug_pair, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-		if (PC.valid && (memcmp(ok, PC.opt_key, sizeof(ok)) || memcmp(tk, PC.tun_key, sizeof(tk)))) PC.valid = false;
-		if (!PC.valid) memcpy(PC.opt_key, ok, sizeof(ok)), memcpy(PC.tun_key, tk, sizeof(tk)), PC.has_groups = false, PC.wide_state = 0;
-	}
-	int64_t max_len = 0, max_bound = 0;
-	if (PC.valid) max_len = PC.max_len, max_bound = PC.max_bound;
-	else {
-		for (int32_t i = 0; i < b->n; ++i) {
-			max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
-			max_bound = std::max(max_bound, penalty_bound(*opt, b->h_tl[i], b->h_ql[i], true));
-		}
-		PC.max_len = max_len, PC.max_bound = max_bound, PC.valid = true;
-	}
-	if (max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
-	const int slots = 1 << 30; // as many as the chosen kernel can keep resident (run_batch_kernel bounds it)
-	if (b->debug_pair >= 0 && ensure(g, g->dbg, (size_t)8 * (max_bound + 2))) return -1;
+	revalidate_plan(g, b, *opt, P0);
+	if (PC.max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
+	if (b->debug_pair >= 0 && ensure(g, g->dbg, (size_t)8 * (PC.max_bound + 2))) return -1;
 	const bool was_busy = b->busy;
 	b->busy = true;
 	PC.wide_measured = false;
-	g->queue_next = 0, g->lane_set_next = 0;
-	// Every pair "not run", CIGAR pool and work counters at zero: one small kernel — unless the result arrays can be written from here
-	// (the pinned result page of a small score-only batch: the single pair of a drop-in call) or came up initialised with the batch
-	// (a small batch's first align); the kernels of such a call then run without a work counter where they can (run_batch_kernel).
-	bool preset = false;
-	if (b->out_in_pin && !was_busy) {
-		for (int32_t i = 0; i < b->n; ++i) b->d_status[i] = -1, b->d_s[i] = -2;
-		preset = true;
-	} else if (b->results_preinit) preset = true;
-	b->results_preinit = false;
-	g->queue_clean = !preset;
-	b->cig_block_left = kCigBlockGrid;
-	if (!preset && launch_reset(b->d_status, b->d_s, b->n, b->d_cig_head, (int32_t*)g->queue.p, kQueueInts, g->stream)) { g->err = "kernel launch failed (reset)"; return -1; }
-	std::fill(b->h_flags.begin(), b->h_flags.end(), 0);
-	// a few long pairs: each one gets the whole device in turn
-	const Penalty P0 = make_penalty(*opt);
-	// (round 3: from 20 000 bases of target + query on, a batch of up to sixteen pairs is faster on the whole-device kernel than one
-	// workgroup per pair on any other — 1 x 12 kb 4.1 against 6.4 ms, 16 x 25 kb 11.5 / 20.5, 1 x 32 kb 9.6 / 26.1, a single 10 kb pair
-	// 3.4 against 5.8 ms on the packed band kernel; profiles/r03/few_long_pairs.txt)
-	// (with traceback already from 15 000 on: 1 x 10 kb 5.1 against 7.2 ms on the packed band kernel, 16 x 8 kb 5.2 / 6.2)
-	const int64_t coop_len = g->coop_min_len > 0 ? g->coop_min_len : ((opt->flag & MWF_F_CIGAR) ? 15000 : 20000);
-	// The whole-device kernel takes time ~ (tl+ql) per round of pairs side by side (each on its own group of workgroups); the generic kernel
-	// runs up to 256 (512) pairs at once in time ~ (tl+ql)^2.  Measured at 3 % divergence (profiles/few_long_pairs.py, round 3): 50 kb pairs
-	// 22 ms per round of 16 against 60 ms for any number of them on the generic kernel, 100 kb pairs 44 ms per round of 8 against 245 ms,
-	// 150 kb pairs 68 ms against 545 ms — the whole-device kernel wins while the batch needs fewer than about 2.7 (tl+ql)/100 000 rounds.
-	bool coop = g->force_kind == 1;
-	int n_cu_coop = 0;
-	if (coop || (g->force_kind < 0 && max_len >= coop_len && coop_supported(P0))) {
-		n_cu_coop = coop_grid_limit(g);
-		const int coop_side_by_side = n_cu_coop > 0 ? std::max(1, n_cu_coop / coop_group_size(n_cu_coop, max_len, false, sys_owned_cols(g->sys_p, 4))) : 1;
-		// (low-memory mode: the alternative is the generic kernel's two-pass form, three times its high-memory time — 17 x 30 kb @ 5 % 186 ms against 50 ms per round of
-		// sixteen here, 48 x 100 kb @ 3 % 694 ms against 555 ms in six rounds of eight: at least four rounds, where the rule above allowed one round of 30 kb pairs;
-		// profiles/r06/routing_survey_long_before.txt, _after.txt)
-		const bool lowmem_call = (opt->flag & MWF_F_CIGAR) && opt->step > 0;
-		const int64_t coop_rounds = lowmem_call ? std::max<int64_t>(4, max_len * 32 / 1000000) : std::max<int64_t>(1, max_len * 27 / 1000000);
-		int64_t coop_max_pairs = std::max<int64_t>(1, std::min<int64_t>(256, coop_rounds * coop_side_by_side));
-		if (max_len < 65536) coop_max_pairs = std::min<int64_t>(coop_max_pairs, lowmem_call ? 48 : 16); // (measured up to sixteen)
-		coop = coop || b->n <= coop_max_pairs;
-	}
-	if (coop) {
-		if (!coop_supported(P0)) { g->err = "whole-device kernel does not support these penalties"; return -2; }
-		if (n_cu_coop < 1) { g->err = "whole-device kernel cannot be made resident"; return -1; }
-		std::vector<int32_t> idx(b->h_order.begin(), b->h_order.end());
-		std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; }); // longest first
-		for (size_t at = 0; at < idx.size();) {
-			const int64_t len0 = (int64_t)b->h_tl[idx[at]] + b->h_ql[idx[at]];
-			const int Gs = coop_group_size(n_cu_coop, len0, false, sys_owned_cols(g->sys_p, 4));
-			const size_t n_side = std::min<size_t>(idx.size() - at, (size_t)std::max(1, n_cu_coop / Gs));
-			const bool last = at + n_side == idx.size();
-			if (n_side <= 1 || b->debug_pair >= 0) { // alone (also: band traces are single-pair diagnostics)
-				if (run_coop_pair(g, b, *opt, idx[at], at == 0, at + 1 == idx.size())) return -1;
-				at += 1;
-				continue;
-			}
-			if (run_coop_group(g, b, *opt, std::vector<int32_t>(idx.begin() + at, idx.begin() + at + n_side), Gs, at == 0, last)) return -1;
-			at += n_side;
+	bool preset = false, whole_device = false;
+	if (reset_results(g, b, was_busy, preset)) return -1;
+	if (const int rc = route_whole_device(g, b, *opt, P0, PC.max_len, whole_device)) return rc;
+	if (!whole_device) {
+		ClassRule R = make_rule(g, b, *opt, P0);
+		ClassPlan cp;
+		if (PC.has_groups) { // same lengths, same options, same tunables as last time: classes, order (already on the device) and maxima as they were
+			b->h_class = PC.cls0, b->h_flags = PC.flags0;
+			std::copy(PC.gi, PC.gi + kNumClasses, cp.gi);
+			cp.mid_bytes = PC.mid_bytes;
+		} else {
+			std::vector<int8_t> cls((size_t)b->n); // class of every pair
+			classify_and_group(g, b, R, cls, cp);
+			if (order_pairs(g, b, cls, cp)) return -1;
+			PC.cls0 = b->h_class, PC.flags0 = b->h_flags, PC.mid_bytes = cp.mid_bytes, PC.has_groups = true;
+			std::copy(cp.gi, cp.gi + kNumClasses, PC.gi);
 		}
-		b->aligned = true;
-		return 0;
-	}
-	// Size classes.  One long pair must not push a thousand short ones onto the slow kernel (mwf_wfa_chain's gap fills are
-	// exactly such a mix): pairs are grouped by what their window can grow to, and every group runs on the kernel that suits
-	// it — generic (largest workspace) first, so that later groups never have to grow a buffer.  Kernel and block size forced
-	// by the caller (tests, tuning) keep the whole batch in one group.
-	// Low-memory mode (opt.step > 0): a pair whose penalty cannot reach `step` never takes a snapshot (the first one is due at
-	// penalty step-1, miniwfa.c:585), so its low-memory result IS its high-memory result, n_iter included — such pairs (the
-	// gap fills of mwf_wfa_auto's chain fallback, which inherit step = 5000) run in the classes as high-memory pairs; only
-	// genuinely long pairs go through the two-pass kernel (group 5).
-	const bool low_mem = cigar && opt->step > 0;
-	const bool classes = g->force_kind < 0 && g->block == 0 && band2_supported(P0) && g->band_pack != 0;
-	// Penalties the packed band kernel is not instantiated for (gap extensions other than (2,1), (2,2), (1,1): minimap2's asm5 has 3 and 1) leave the generic kernel for
-	// everything above — but the lane and mid kernels read their penalties at run time: read batches and a few mid-size pairs still get them (20 000 x 150 bp with
-	// e1 = 3: 4.8 ms on the generic kernel, a thirteenth of that on the lane kernel).  What outgrows them goes to the generic kernel.
-	const bool small_only = g->force_kind < 0 && g->block == 0 && !band2_supported(P0) && g->band_pack != 0;
-	// groups 0-4: the size classes, 5: two-pass low-memory pairs, 6-9: classes 1-4 again for the pairs the host knows not to be
-	// plain A/C/G/T (byte-wise sequence copy from the start)
-	// 10: short pairs on the one-diagonal-per-lane kernel (mwf_lane.hip); what outgrows its 64 columns moves to the band classes
-	// 11: mid-size pairs of a small batch on the one-workgroup-per-pair, rings-in-LDS kernel (mwf_mid.hip); what outgrows its span moves to the band classes
-	typedef mwf_gpu_batch_t::PlanCache::GI GroupInfo;
-	GroupInfo gi[17];
-	bool mid_bytes = false;
-	// ("alpha16", gap extensions (2,1)) 15: the class-3 pairs of classes 1-4 on the 4-bit 512-thread geometry, 16: those of classes 13 and 14 on the 4-bit span geometry
-	// (mwf_band2_nib.hip); hand-backs as for the plain pairs of their h_class — window overflow to the next 4-bit geometry, then the generic kernel
-	auto nib_pair = [&](int32_t i) {
-		return g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(P0) && !low_mem &&
-		       (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3;
-	};
-	// (12: the pairs of class 10 the host knows not to be plain A/C/G/T — reads with an N —: the lane kernel on byte-wise copies)
-	// 13: pairs too long (or with windows too wide) for the 512-thread packed geometry on its 1024-thread span geometry: targets of up to ~60 kb on biased
-	// 16-bit offsets, windows of up to ~16 000 columns; what outgrows it moves to the generic kernel
-	// 14: pairs of up to ~21 kb per sequence whose worst-case penalty rules out plain 16-bit offsets: the 512-thread geometry with five or six chunk slots, which computes on
-	// biased offsets with range checks like the span geometry but keeps two pairs per CU (windows of up to 9920 / 11 968 columns; what outgrows them moves to the span geometry).
-	// Built for every set the band kernel takes (band2_biased512_supported): where e2 == 2 — main.c's -a preset — the class starts at ~6.6 kb, 1024 x 10 kb batches are its.
-	static const int run_order[17] = {5, 0, 13, 14, 16, 1, 15, 6, 2, 7, 3, 8, 4, 9, 11, 10, 12}; // largest workspace first
-	if (PC.has_groups) { // same lengths, same options, same tunables as last time: classes, order (already on the device) and maxima as they were
-		b->h_class = PC.cls0, b->h_flags = PC.flags0;
-		for (int c = 0; c < 17; ++c) gi[c] = PC.gi[c];
-		mid_bytes = PC.mid_bytes;
-	} else {
-		const bool lane_ok = g->lane_max_len > 0 && lane_supported(P0);
-		const int mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
-		// the mid kernel (a workgroup per pair, one per CU) serves a FEW pairs: a batch of at most mid_cap pairs, or the at most mid_cap pairs of a
-		// larger batch that are neither short reads (lane kernel) nor long (classes 0-2 ... see below) — mwf_wfa_chain's gap fills are hundreds of
-		// tiny pairs and a handful of longer ones, and the handful sets the call's time
-		const bool mid_batch = g->force_kind < 0 && g->block == 0 && mid_cap > 0 && mid_supported(P0);
-		const bool mid_ok = mid_batch && b->n <= mid_cap;
-		const bool know_acgt = !b->h_acgt.empty() && g->seq2bit != 0;
-		const bool pack_pen = g->band_pack != 0 && band2_supported(P0);
-		std::vector<int8_t> cls((size_t)b->n); // group of every pair
-		int32_t count[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-		const bool span_pen = pack_pen && g->band_span != 0 && g->seq2bit != 0;
-		// The classes' length limits stand for "the window stays inside the span at ~5 % divergence".  Where the batch's own divergence is known
-		// (estimate_divergence: batches built from host memory) the lengths are weighed by it: three times as diverged = as if three times as long.
-		// Only upwards of the prior, and a little downwards: a class too narrow costs a second run, one too wide a few per cent.
-		const double div_r = b->div_est > 0 && g->div_aware ? std::min(8.0, std::max(0.7, (double)b->div_est / 0.05)) : 1.0;
-		const double div_lane = b->div_est > 0 && g->div_aware ? std::min(8.0, std::max(0.45, (double)b->div_est / 0.05)) : 1.0;
-		// A batch of reads whose lengths straddle the limit is not split for a few pairs: where most of the pairs up to 10 % beyond the limit lie below it, the rest follow
-		// them (2000 x 300 bp with 28 pairs beyond: 0.37 ms as one lane launch, 0.50 with a launch of their own)
-		int64_t lane_limit = mid_ok ? std::min(g->lane_max_len, 320) : g->lane_max_len;
-		if (lane_ok && !mid_ok && (classes || small_only)) {
-			int64_t n_lo = 0, n_hi = 0;
-			for (int32_t i = 0; i < b->n; ++i) {
-				const int64_t w = (int64_t)((double)std::max(b->h_tl[i], b->h_ql[i]) * div_lane);
-				if (std::abs(b->h_tl[i] - b->h_ql[i]) > 24) continue;
-				n_lo += w <= lane_limit, n_hi += w > lane_limit && w <= lane_limit * 11 / 10;
-			}
-			if (n_hi > 0 && n_lo >= n_hi) lane_limit = lane_limit * 11 / 10;
-		}
-		struct PairInfo { int64_t bound, bound1, exp_win; };
-		std::vector<PairInfo> info((size_t)b->n);
-		std::vector<int8_t> mid_cand;   // large batches: pairs the mid kernel would take if they are few
-		int32_t n_cand = 0;
-		if (mid_batch && !mid_ok) mid_cand.assign((size_t)b->n, 0);
-		// class of pair i; allow_mid: the mid kernel may take it
-		auto classify = [&](int32_t i, bool allow_mid) -> int {
-			const int64_t tl = b->h_tl[i], ql = b->h_ql[i], len = tl + ql;
-			// A pair of very different lengths must open a gap of |tl - ql|: its window reaches that diagonal whatever its divergence (two columns per
-			// penalty of the gap, until the matrix ends), so the length limits see it as if it were longer — beyond what indels of a related pair add up
-			// to.  (Found on mwf_wfa_chain's gap fills: a 54 x 740 fill sat in the 64-thread class and was run twice, every call.)
-			const int64_t skew = std::abs(tl - ql), skew_len = 6 * std::max<int64_t>(0, skew - len / 16);
-			const int64_t lenw = (int64_t)((double)len * div_r) + skew_len; // the pair's length as the classes' limits should see it
-			// the window the pair is expected to reach (0.27 (tl+ql) at 5 %), plus 15 %, where the divergence is known: the long classes' length limits
-			// were drawn for ~3 % (configs[4]) and sent 20 kb pairs at 15 % and 50 kb pairs at 5 % through the span geometry for nothing
-			const int64_t exp_win = b->div_est > 0 && g->div_aware ? std::min<int64_t>(len + 1, (int64_t)(6.2 * b->div_est * (double)len) + 64) : 0;
-			const int64_t bound1 = penalty_bound(*opt, tl, ql, false);
-			const int64_t bound = opt->max_s > 0 ? std::min<int64_t>(bound1, (int64_t)opt->max_s + 1) : bound1; // (= penalty_bound(..., true))
-			info[(size_t)i] = PairInfo{bound, bound1, exp_win};
-			const bool step0 = low_mem && bound1 < opt->step;
-			int c = low_mem && !step0 ? 5 : 0;
-			const bool packable = tl + bound < 32767 && pack_pen;
-			if (classes && c == 0) {
-				const int64_t window = std::min<int64_t>(len + 1, 2 * bound + 3);
-				// A window cannot outgrow min(tl+ql+1, 2 x penalty bound + 3); in practice it stays far below tl+ql (a quarter of
-				// it at 5 % divergence), so a pair is also given to a small kernel when it is merely short — if its window does
-				// outgrow that span, finalize() moves it to the wide band kernel, and from there to the generic one.
-				// (a pair too long for the packed band kernel goes to the generic kernel with 16-bit ring rows where those apply: faster than
-				// the unpacked band kernel and no window overflows to re-run, see choose_kernel)
-				// (... unless the span geometry of the packed kernel takes it: windows of up to ~16 000 columns — a 50 kb pair at 3 % —, which is
-				// where the pairs whose windows will mostly fit are drawn: tl + ql below seven spans; bench.py long_batches)
-				const bool nib_i = nib_pair(i); // (its 4-bit copy stands where a plain pair's 2-bit copy does: the long classes admit it)
-				const bool span_ok = span_pen && tl <= kBandSpanMaxSeq && ql <= kBandSpanMaxSeq && (!(know_acgt && !b->h_acgt[i]) || nib_i);
-				if (span_ok && g->band_span == 2) c = 13;
-				// (round 5: the limits leave the mean window at 5 % — 0.27 (tl+ql) — a quarter of margin below each class's widest window; round 4's left 4-18 %,
-				// and 2 kb pairs, just inside the 128-thread class, were re-run at 7.8 %: profiles/r04/chooser_regression.txt)
-				// (... at 5 %.  A batch the sketch puts at 8 % and more outgrows the 64-thread class earlier than its weight says — the sketch reads low up there, and a pair
-				// whose penalty stays below 256 is never shrunk, its window is 2 s + 1: 2000 x 350 bp @ 10 % lost 876 pairs, 20 000 x 380 bp 18 473, to a second run)
-				else if (packable && (window <= kBandMicroWindow || lenw + 1 <= (b->div_est >= 0.06f && g->div_aware ? 1000 : 1400))) c = 4;
-				else if (packable && (window <= kBandTinyWindow || lenw + 1 <= 3600)) c = 3;
-				else if (packable && (window <= kBandSmallWindow || lenw + 1 <= 8200)) c = 2;
-				else if (packable && (lenw + 1 <= 4 * (int64_t)(8 * 3 * 256) || window <= kBandWideWindow)) c = 1;
-				// (tl + ql up to 3.5 of its spans: a 12 kb pair at 5 % needs ~6000 of the 7872 columns; 512 x 15 kb @ 5 % — windows of ~7500 — lost 44 pairs to late
-				// overflows, 30.7 against 24.9 ms on the span geometry from the start)
-				else if (span_ok && band2_biased512_supported(P0) && g->wide_slots != 3 && (exp_win ? exp_win + 768 <= ((int64_t)band2_biased512_chunks() + 8 - 1) * 256 - 64 : len + 1 <= 7 * (int64_t)((band2_biased512_chunks() + 8) * 256) / 2)) c = 14;
-				else if (span_ok && ((exp_win ? exp_win + 768 <= band_span_window() : len + 1 <= 7 * band2_span_chunks() * 256) || window <= band_span_window())) c = 13;
-			}
-			b->h_class[i] = (int8_t)(c == 5 ? 0 : c == 13 ? 5 : c == 14 ? 1 : c);
-			b->h_flags[i] = (int8_t)(step0 ? 1 : 0);
-			// the class the pair's lengths would give it, for the admission to the lane and mid kernels where the band kernel itself cannot serve (their offsets are 16 bits too)
-			int c_adm = c;
-			if (small_only && c == 0 && tl + bound < 32767) {
-				const int64_t window = std::min<int64_t>(len + 1, 2 * bound + 3);
-				c_adm = (window <= kBandMicroWindow || lenw + 1 <= (b->div_est >= 0.06f && g->div_aware ? 1000 : 1400)) ? 4 : (window <= kBandTinyWindow || lenw + 1 <= 3600) ? 3 : 0;
-			}
-			// short pairs: a window of 64 diagonals holds them while the penalty stays below ~45 (a 200 bp pair at 5 %)
-			// (in a batch small enough for the mid kernel the lane kernel keeps the pairs of up to 320 bases: 16 x 400 bp 0.31 ms on the lane
-			// kernel — pairs that outgrow its chunks are re-run — against 0.13 on the mid kernel, 1 x 300 bp 56 against 68 us; profiles/r04/lane_vs_mid.txt)
-			// (the lane kernel's limit is a window — its chunks — and a window is proportional to divergence x length: the weight goes further down for it than for the
-			// classes, 2000 x 450 bp @ 2 % 0.14 against 0.27 ms on the 64-thread geometry; profiles/r06/lane_crossover.txt)
-			const bool to_lane = (classes || small_only) && lane_ok && c_adm >= 1 && c_adm <= 4 && (int64_t)((double)std::max(tl, ql) * div_lane) <= lane_limit && skew <= 24;
-			if (to_lane) c = (know_acgt && !b->h_acgt[i]) ? 12 : 10, b->h_class[i] = (int8_t)(classes ? 4 : 2); // (where an overflow goes: the re-run of "band" pairs takes the mid kernel for a handful, else whatever choose_kernel has for the penalties)
-			// a few mid-size pairs: a workgroup each, rings in LDS (a penalty then costs a fraction of what it costs the band kernels).  Admitted
-			// when the span the LDS can hold beside the sequences covers the window of a pair at ~6 % divergence (about 0.3 (tl+ql)) and the gap its lengths
-			// force — or every column the pair can ever reach; 16-bit offsets.
-			if (mid_batch && !to_lane && c <= 4 && (!low_mem || step0) && tl + bound < 32760) {
-				const int64_t seq_lds = ((tl + 7) & ~7LL) + 16 + ((ql + 7) & ~7LL) + 32;
-				const int64_t window = std::min<int64_t>(len + 1, 2 * bound + 3);
-				const int64_t want = std::min<int64_t>(window, lenw * 34 / 100 + 128) + 2 * P0.nH;
-				int groups = (int)std::min<int64_t>((window + 2 * P0.nH + 63) / 64, 128);
-				while (groups > 1 && mid_lds_bytes(P0, groups, seq_lds) > 158 * 1024) --groups;
-				// (the span lies around the middle of diagonals 0 and ql - tl, mwf_mid.hip: all the columns a window can reach — the matrix, or what the penalty
-				// bound allows either side of diagonal 0 — plus the dead margins)
-				const int64_t C = (int64_t)groups * 64, left = tl + 1 + (ql - tl) / 2 - C / 2, right = left + C - 1;
-				const bool holds_all = std::max<int64_t>(1, tl + 1 - (bound + 1)) - P0.nH >= left && std::min<int64_t>(len + 1, tl + 1 + bound + 1) + P0.nH <= right;
-				if (mid_lds_bytes(P0, groups, seq_lds) <= 158 * 1024 && (holds_all || (C >= want && skew < groups * 32))) {
-					if (!allow_mid) {
-						// (a large batch: counted; the pairs move to the mid kernel afterwards if they are few, and only the band kernels' SMALL classes give
-						// pairs away — wide windows are the 512-thread geometry's work whatever their number)
-						if (!mid_cand.empty() && c_adm >= 3 && c_adm <= 4 && !mid_cand[(size_t)i]) mid_cand[(size_t)i] = 1, ++n_cand;
-					} else {
-						b->h_class[i] = (int8_t)((c >= 1 && c <= 4) || (classes && packable) ? 2 : 0); // where an overflow goes: the wide packed band kernel, else generic
-						c = 11;
-						mid_bytes |= know_acgt && !b->h_acgt[i]; // a pair the host knows not to be plain A/C/G/T: the (few) pairs of this class all take the byte-wise copy
-					}
-				}
-			}
-			if (((c >= 1 && c <= 4 && packable) || c == 13 || c == 14) && nib_pair(i)) c = c <= 4 ? 15 : 16;
-			else if (c >= 1 && c <= 4 && know_acgt && !b->h_acgt[i] && packable) c += 5;
-			return c;
-		};
-		for (int32_t i = 0; i < b->n; ++i) cls[(size_t)i] = (int8_t)classify(i, mid_ok);
-		if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] classes of %d pairs: divergence estimate %.4f (weight %.2f)\n", b->n, (double)b->div_est, div_r);
-		if (n_cand > 0 && n_cand <= mid_cap)
-			for (int32_t i = 0; i < b->n; ++i)
-				if (mid_cand[(size_t)i]) cls[(size_t)i] = (int8_t)classify(i, true);
-		for (int32_t i = 0; i < b->n; ++i) {
-			const int64_t tl = b->h_tl[i], ql = b->h_ql[i], len = tl + ql;
-			const int c = cls[(size_t)i];
-			const PairInfo &pi = info[(size_t)i];
-			GroupInfo &G = gi[c];
-			++count[c];
-			G.max_len = std::max(G.max_len, len), G.max_bound = std::max(G.max_bound, pi.bound);
-			G.max_bound1 = std::max(G.max_bound1, pi.bound1);
-			// (the mid class: the window its pairs are expected to reach, forced gap included — its launch picks the workgroup size by it)
-			const int64_t exp_win = c == 11 ? std::min<int64_t>(len + 1, (int64_t)((double)len * div_r * 0.28) + 2 * std::abs(tl - ql)) : pi.exp_win;
-			G.max_tl = std::max<int64_t>(G.max_tl, tl), G.max_exp_win = std::max(G.max_exp_win, exp_win);
-			G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, ((tl + 3) & ~3LL) + 8 + ((ql + 3) & ~3LL) + 16);
-		}
-		// The processing order: groups in run order, longest first inside a group (the persistent workgroups finish together; the classes on the shared
-		// work counter then by predicted work, below).  h_order is
-		// already sorted longest first (batch_common) and that order is stable: one pass over it deals the pairs to their groups.
-		std::vector<int32_t> start(17, 0), order((size_t)b->n);
-		{
-			int32_t at = 0;
-			for (int c : run_order) start[c] = at, at += count[c], gi[c].n = count[c];
-		}
-		if (b->h_len_order.empty()) {
-			b->h_len_order.resize((size_t)b->n);
-			std::iota(b->h_len_order.begin(), b->h_len_order.end(), 0);
-			std::stable_sort(b->h_len_order.begin(), b->h_len_order.end(), [&](int32_t x, int32_t y) {
-				return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y];
-			});
-		}
-		for (int32_t i : b->h_len_order) order[(size_t)start[cls[i]]++] = i;
-		// The classes on the shared work counter — the 512-thread geometries (1, its biased copy 14, its byte-wise copy 6) and the 1024-thread span
-		// geometry (13) — are dealt by predicted WORK, largest first: in an equal-length batch "longest first" says nothing about how long a pair takes.
-		// 1024 x 10 kb at 5 %: s 2118 ... 2838 (sd 118) on one length; the pairs dealt last finished far apart while CUs idled (the drain).
-		// The estimate: s ~ (tl + ql) x d, d from the share of the query's 8-mers found in the target over the WHOLE pair (correlation 0.88 with s;
-		// the batch sketch's 1500-base prefix 0.34).  A class that fits on the device at once (no more pairs than workgroups) has nothing to deal.
-		bool reorder = false;
-		for (int c : {13, 14, 16, 1, 15, 6}) reorder |= count[c] > 2 * g->n_cu; // (two workgroups per CU on the 512-thread geometries; the span geometry holds fewer)
-		if (reorder && g->work_order != 0 && (g->work_order != 2 || (int32_t)b->h_iter.size() == b->n)) {
-			const int32_t lo = start[13] - count[13], hi = start[6]; // (run_order keeps the four side by side)
-			std::vector<double> key((size_t)b->n, 0.0);
-			if (g->work_order == 1) {
-				// one workgroup per pair reads both sequences from the device (at align: the caller's arrays need only be valid then); the pair ids go up in
-				// the order array, which gets the final order below
-				if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{order.data() + lo, (size_t)(hi - lo) * 4}})) return -1;
-				b->h_order.clear();
-				if (launch_pair_sketch(b->d_seqs, b->alpha_active ? b->d_rt_off : b->d_t_off, b->d_tl, b->alpha_active ? b->d_rq_off : b->d_q_off, b->d_ql, b->d_order, hi - lo, b->d_dbg4, g->stream)) { g->err = "kernel launch failed (pair sketch)"; return -1; }
-				std::vector<int32_t> hits((size_t)(hi - lo));
-				HIP_TRY(g, hipMemcpyAsync(hits.data(), b->d_dbg4, hits.size() * 4, hipMemcpyDeviceToHost, g->stream)); // (scratch behind the results: written by this align's kernels only with MWF_F_DEBUG)
-				HIP_TRY(g, hipStreamSynchronize(g->stream));
-				for (int32_t k = lo; k < hi; ++k) {
-					const int32_t i = order[(size_t)k], tl = b->h_tl[i], ql = b->h_ql[i];
-					key[(size_t)i] = (double)((int64_t)tl + ql) * sketch_divergence(hits[(size_t)(k - lo)], std::max(ql - 7, 0), tl);
-				}
-			} else if (g->work_order == 2) {
-				for (int32_t k = lo; k < hi; ++k) key[(size_t)order[(size_t)k]] = (double)b->h_iter[(size_t)order[(size_t)k]];
-			}
-			for (int c : {13, 14, 16, 1, 15, 6}) {
-				if (count[c] <= 2 * g->n_cu) continue;
-				const auto first = order.begin() + (start[c] - count[c]), last = order.begin() + start[c];
-				if (g->work_order == 3) std::reverse(first, last); // (shortest first: the other bound of the measurement)
-				else std::sort(first, last, [&](int32_t x, int32_t y) {
-					if (key[(size_t)x] != key[(size_t)y]) return key[(size_t)x] > key[(size_t)y];
-					const int64_t lx = (int64_t)b->h_tl[x] + b->h_ql[x], ly = (int64_t)b->h_tl[y] + b->h_ql[y];
-					return lx != ly ? lx > ly : x < y;
-				});
-			}
-		}
-		if (order != b->h_order) {
-			b->h_order.swap(order);
-			if (upload_segments(g, (char*)b->d_order, std::vector<Seg>{Seg{b->h_order.data(), b->h_order.size() * 4}})) return -1; // (waits for earlier work on the stream first)
-		}
-		PC.cls0 = b->h_class, PC.flags0 = b->h_flags, PC.mid_bytes = mid_bytes, PC.has_groups = true;
-		for (int c = 0; c < 17; ++c) PC.gi[c] = gi[c];
-	}
-	int n_groups = 0, done_groups = 0;
-	for (const GroupInfo &G : gi) n_groups += G.n > 0;
-	mwf_opt_t opt_hi = *opt;
-	opt_hi.step = 0;
-	size_t at = 0;
-	for (int c : run_order) {
-		const GroupInfo &G = gi[c];
-		if (G.n == 0) continue;
-		++done_groups;
-		int ran = 0;
-		const int cc = c == 16 ? 7 : c == 15 ? 1 : c == 14 ? 8 : c == 13 ? 7 : c == 11 ? 6 : (c == 10 || c == 12) ? 5 : c > 5 ? c - 5 : c;
-		// (the lane class of a batch of reads hands its overflows to a follow-up launch on the device, below)
-		const bool lane_retry = (c == 10 || c == 12) && g->dev_retry && G.n >= 1024 && !preset && g->force_kind < 0 && g->block == 0 && mid_supported(P0) && G.max_len <= 1200 &&
-		                        G.max_tl + G.max_bound < 32760 && !low_mem;
-		if (lane_retry) g->retry_mode = 1, g->retry_slot = c == 12 ? 1 : 0;
-		g->acgt_off_once = (c > 5 && c < 10) || (c == 11 && mid_bytes) || c == 12;
-		// (a forced kernel or block keeps the batch in one group: the 4-bit form then only where every pair of it is class 3)
-		bool all_nib = !classes && c == 0 && g->force_kind != 0;
-		for (int32_t i = 0; all_nib && i < b->n; ++i) all_nib = nib_pair(i);
-		g->nib_once = c == 15 || c == 16 || all_nib;
-		const bool wide_c = c == 1 || c == 15; // the classes on the 512-thread geometry of three or four slots
-		const int rc = run_batch_kernel(g, b, c == 5 ? *opt : opt_hi, b->d_order + at, G.n, slots, G.max_len, G.max_bound, G.max_bound1,
-		                                done_groups == 1, (classes || c >= 11) ? (c == 0 || c == 5 ? 0 : 2) : -1, G.max_tl, G.max_seq_lds, lane_retry ? 0 : done_groups == n_groups,
-		                                cc == 8 ? 514 : cc == 7 ? 1024 : cc == 6 ? 33 : cc == 5 ? 32 : cc == 4 ? 64 : cc == 3 ? 128 : cc == 2 ? 256 : 0, &ran,
-		                                (wide_c && (g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean))) ? kBandWide4Window : (c == 14 || c == 11) ? G.max_exp_win : 0);
-		g->retry_mode = 0;
-		g->nib_once = false;
-		if (wide_c && g->wide_slots == 0 && PC.wide_state == 0 && g->queue_clean && ran == 2 && g->stats.block == 512) PC.wide_measured = true;
-		// Batches of reads: what the lane kernel hands back (a window that left its chunks: one read in tens of thousands) is re-run by a follow-up launch of
-		// the mid kernel, whose span holds the widest window such a pair can have — from a list the lane kernel filled ON THE DEVICE.  Round 4 read the status
-		// words back, launched, waited and read them again: ~0.2 ms behind a 0.5 ms launch.  (An empty list costs the launch of a few idle workgroups.)
-		if (rc == 0 && lane_retry) {
-			const mwf_gpu_stats_t keep = g->stats;
-			g->retry_mode = 2;
-			g->acgt_off_once = c == 12;
-			int ran2 = 0;
-			// (every entry of the list — the mid kernel strides over it by its grid —, on at most 32 workgroups: an empty list costs the launch of a few idle ones)
-			const int rc2 = run_batch_kernel(g, b, opt_hi, b->d_retry_ids + g->retry_slot * kRetryCap, kRetryCap, std::min(slots, 32), G.max_len, G.max_bound, G.max_bound1, false, 2, G.max_tl, G.max_seq_lds,
-			                                 done_groups == n_groups, 33, &ran2, 0);
-			g->retry_mode = 0, g->acgt_off_once = false;
-			const int32_t launches = g->stats.n_launches;
-			g->stats = keep, g->stats.n_launches = launches; // (the statistics describe the class's own launch)
-			if (rc2) return -1;
-			b->dev_retry_used = true;
-		}
-		g->acgt_off_once = false;
-		if (rc) return -1;
-		// (bit 64: the pair ran on the plain three-slot 512-thread geometry — the only one whose LATE overflow says "this batch's wide class needs four slots")
-		const bool three_slots = wide_c && ran == 2 && g->stats.block == 512 && !(g->wide_slots == 4 || (g->wide_slots == 0 && PC.wide_state != 1 && g->queue_clean));
-		for (size_t j = at; j < at + (size_t)G.n; ++j) {
-			const int32_t i = b->h_order[j];
-			b->h_kind[i] = (int8_t)ran, b->h_flags[i] = (int8_t)((b->h_flags[i] & ~64) | (three_slots ? 64 : 0));
-		}
-		at += (size_t)G.n;
+		if (launch_classes(g, b, *opt, R, cp, preset)) return -1;
 	}
 	b->aligned = true;
 	return 0;
@@ -1186,13 +1145,13 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 		for (size_t i = 0; i < n; ++i) {
 			const int32_t st = b->h_status[i];
 			if (st == ST_OK || st == ST_STOPPED) continue;
-			const int kind = b->h_kind[i], step0 = b->h_flags[i] & 1;
+			const int kind = b->h_kind[i], step0 = b->h_flags[i] & FLAG_STEP0;
 			static const bool dbg_route = getenv("MWF_DEBUG_REROUTE") != nullptr; // (diagnostics: why a pair is run again)
 			if (dbg_route) fprintf(stderr, "[libmwf_hip] re-route: pair %zu (tl %d ql %d) status %d kind %d class %d flags %d n_iter word %lld round %d\n", i, b->h_tl[i], b->h_ql[i], st, kind, (int)b->h_class[i], (int)b->h_flags[i], (long long)b->h_iter[i], round);
 			if (st == ST_BAND_OVERFLOW && kind == 0) {
 				to_generic32[step0].push_back((int32_t)i); // an offset outgrew the generic kernel's 16-bit ring rows: 32-bit rows
-			} else if (st == ST_ALPHABET && kind == 2 && b->h_class[i] == 5) {
-				b->h_class[i] = 0, to_generic[step0].push_back((int32_t)i); // (the span geometry has no byte-wise form)
+			} else if (st == ST_ALPHABET && kind == 2 && b->h_class[i] == CLS_SPAN) {
+				b->h_class[i] = CLS_GENERIC, to_generic[step0].push_back((int32_t)i); // (the span geometry has no byte-wise form)
 			} else if (st == ST_ALPHABET && kind == 2) {
 				to_band_bytes[step0].push_back((int32_t)i); // not plain ACGT: the byte-wise band kernel of the same class
 			} else if (st == ST_BAND_OVERFLOW && kind == 2) {
@@ -1201,31 +1160,32 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 				const int64_t est = b->h_iter[i] < 0 ? -b->h_iter[i] : 0;
 				// (a pair of the wide class that outgrew its three chunk slots per wave LATE — that geometry carries no forecast — is re-run alone, ~7 ms for a
 				// 10 kb pair beside the batch's 17: the next align of this batch takes the four-slot geometry for the class)
-				// (only a pair that really ran on that geometry says so: class-14 pairs on biased offsets and re-runs of mid / lane pairs carry class 1 as well)
-				if ((b->h_flags[i] & 64) && est == 0) b->plan.wide_state = 2;
-				b->h_flags[i] &= ~64;
+				// (only a pair that really ran on that geometry says so: CLS_BIASED pairs on biased offsets and re-runs of mid / lane pairs carry CLS_WIDE as well)
+				if ((b->h_flags[i] & FLAG_THREE_SLOTS) && est == 0) b->plan.wide_state = 2;
+				b->h_flags[i] &= ~FLAG_THREE_SLOTS;
 				// (... only when the forecast is half again beyond the widest class: it is an estimate, and the generic kernel is several times slower)
 				// what outgrew (or is forecast to outgrow) the 512-thread geometry: the 1024-thread span geometry, if the pair fits that
-				const bool span_ok = b->h_class[i] >= 1 && b->h_class[i] <= 4 && g->band_span != 0 && g->seq2bit != 0 && g->force_kind < 0 && g->block == 0 &&
+				const bool span_ok = is_band_size_class(b->h_class[i]) && g->band_span != 0 && g->seq2bit != 0 && g->force_kind < 0 && g->block == 0 &&
 				                     b->h_tl[i] <= kBandSpanMaxSeq && b->h_ql[i] <= kBandSpanMaxSeq && est <= band_span_window();
 				// (a forecast the four-slot 512-thread geometry holds — the re-run takes four slots for it, see rerun(); beyond it the span geometry at once:
 				// round 4 sent forecasts of up to 1.5 x the THREE-slot window here and re-ran them on three slots, which by their own forecast could not hold them)
-				if (b->h_class[i] >= 2 && est <= kBandWide4Window) b->h_class[i] = 1, to_band_wide[step0].push_back((int32_t)i);
-				else if (span_ok) b->h_class[i] = 5, to_band_span[step0].push_back((int32_t)i);
+				// (every class but generic and wide: a pair of the span geometry whose forecast is that small takes this way too, as it always has)
+				if (b->h_class[i] != CLS_GENERIC && b->h_class[i] != CLS_WIDE && est <= kBandWide4Window) b->h_class[i] = CLS_WIDE, to_band_wide[step0].push_back((int32_t)i);
+				else if (span_ok) b->h_class[i] = CLS_SPAN, to_band_span[step0].push_back((int32_t)i);
 				// (a forecast also says whether the generic kernel's 16-bit ring rows can hold the pair — offsets up to 65 532, i.e. target length
 				// + final penalty, about half the window: 50 kb pairs at 15 % ran them for nothing before taking the 32-bit rows)
-				else if (est > 0 && (int64_t)b->h_tl[i] + est / 2 + 64 > 65000) b->h_class[i] = 0, to_generic32[step0].push_back((int32_t)i);
-				else b->h_class[i] = 0, to_generic[step0].push_back((int32_t)i);
-			} else if (kind == 1 && st == ST_INTERNAL && !(b->h_flags[i] & 8)) {
+				else if (est > 0 && (int64_t)b->h_tl[i] + est / 2 + 64 > 65000) b->h_class[i] = CLS_GENERIC, to_generic32[step0].push_back((int32_t)i);
+				else b->h_class[i] = CLS_GENERIC, to_generic[step0].push_back((int32_t)i);
+			} else if (kind == 1 && st == ST_INTERNAL && !(b->h_flags[i] & FLAG_COOP_GAVE_UP)) {
 				// a wait between workgroups of the whole-device kernel ran into its spin limit (they were not all resident, e.g.
 				// the device is shared): the one-workgroup kernel needs no such thing
 				fprintf(stderr, "[libmwf_hip] warning: whole-device kernel gave up waiting for a workgroup on pair %d; re-running it on one workgroup (slow)\n", (int)i);
-				b->h_flags[i] |= 8;
+				b->h_flags[i] |= FLAG_COOP_GAVE_UP;
 				to_generic[step0].push_back((int32_t)i);
 			} else if (kind == 1 && (st == ST_BAND_OVERFLOW || st == ST_TB_OVERFLOW || st == ST_SNAP_OVERFLOW)) {
-				if (b->h_flags[i] & 2) coop_alone.push_back((int32_t)i); // had a share of the workgroups and of the arena: now alone
-				else if (st == ST_BAND_OVERFLOW && (b->h_flags[i] & 32) && !(b->h_flags[i] & 16)) {
-					b->h_flags[i] |= 16; // its window outgrew the 64-column slots: again with 256-column ones
+				if (b->h_flags[i] & FLAG_COOP_SHARED) coop_alone.push_back((int32_t)i); // had a share of the workgroups and of the arena: now alone
+				else if (st == ST_BAND_OVERFLOW && (b->h_flags[i] & FLAG_COOP_NARROW) && !(b->h_flags[i] & FLAG_COOP_WIDE)) {
+					b->h_flags[i] |= FLAG_COOP_WIDE; // its window outgrew the 64-column slots: again with 256-column ones
 					coop_alone.push_back((int32_t)i);
 				} else if (st == ST_BAND_OVERFLOW) {
 					if (!coop_warned) fprintf(stderr, "[libmwf_hip] warning: wavefront of pair %d outgrew the whole-device kernel's span; re-running it on one workgroup (slow)\n", (int)i);
@@ -1262,7 +1222,7 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 			return g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(Pn) && !pl_low_mem(b->opt) &&
 			       (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3;
 		};
-		auto rerun1 = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast, int geom, bool nib) -> int {
+		auto rerun1 = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast, Geom geom, CopyForm copy, bool ring16_allowed) -> int {
 			if (ids.empty()) return 0;
 			int64_t hint = 0;
 			if (use_forecast) { // every pair of the re-run came back with a forecast: the class that holds the widest of them (+ 25 %)
@@ -1271,18 +1231,19 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 					hint = std::max<int64_t>(hint, -b->h_iter[i] * 5 / 4 + 64);
 				}
 				// (every forecast of this re-run is at most kBandWide4Window: the margin must not push the hint past the four-slot geometry, back onto three slots)
-				if (hint > kBandWide4Window && want_kind == 2 && geom == 0) hint = kBandWide4Window;
+				if (hint > kBandWide4Window && want_kind == 2 && geom == GEOM_CHOOSE) hint = kBandWide4Window;
 			}
 			std::stable_sort(ids.begin(), ids.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; });
 			const mwf_opt_t &o = step0 ? opt_hi : b->opt;
-			int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0;
+			GroupInfo G;
 			for (int32_t i : ids) {
-				max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
-				max_bound = std::max(max_bound, penalty_bound(o, b->h_tl[i], b->h_ql[i], true));
-				max_bound1 = std::max(max_bound1, penalty_bound(o, b->h_tl[i], b->h_ql[i], false));
-				max_tl = std::max<int64_t>(max_tl, b->h_tl[i]);
-				max_seq_lds = std::max<int64_t>(max_seq_lds, (((int64_t)b->h_tl[i] + 3) & ~3LL) + 8 + (((int64_t)b->h_ql[i] + 3) & ~3LL) + 16);
+				G.max_len = std::max<int64_t>(G.max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+				G.max_bound = std::max(G.max_bound, penalty_bound(o, b->h_tl[i], b->h_ql[i], true));
+				G.max_bound1 = std::max(G.max_bound1, penalty_bound(o, b->h_tl[i], b->h_ql[i], false));
+				G.max_tl = std::max<int64_t>(G.max_tl, b->h_tl[i]);
+				G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, (((int64_t)b->h_tl[i] + 3) & ~3LL) + 8 + (((int64_t)b->h_ql[i] + 3) & ~3LL) + 16);
 			}
+			G.n = (int32_t)ids.size();
 			DevBuf &tmp = g->retry_ids; // the ids of this re-run (the previous re-run's kernels are through: every rerun() ends with a stream synchronisation)
 			if (ensure(g, tmp, std::max<size_t>(ids.size() * 4, 4096))) return -1;
 			int rc = upload_segments(g, (char*)tmp.p, std::vector<Seg>{Seg{ids.data(), ids.size() * 4}});
@@ -1292,42 +1253,39 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 			// of band kernel in every align of the 40 000-pair batch, profiles/r04/rocprof_lane_kernel_40000x150bp.txt)
 			const Penalty Pm = make_penalty(o);
 			const int mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
-			const bool to_mid = want_kind == 2 && use_forecast && !nib && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(Pm) && max_len <= 1200 &&
-			                    max_tl + max_bound < 32760 && !(pl_low_mem(o));
-			g->nib_once = nib;
-			if (rc == 0) rc = run_batch_kernel(g, b, o, (const int32_t*)tmp.p, (int32_t)ids.size(), slots, max_len, max_bound, max_bound1, false,
-			                                   want_kind, max_tl, max_seq_lds, 0, to_mid ? 33 : geom, &ran, hint);
-			g->nib_once = false;
+			const bool to_mid = want_kind == 2 && use_forecast && copy != COPY_NIB && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(Pm) && G.max_len <= 1200 &&
+			                    G.max_tl + G.max_bound < 32760 && !(pl_low_mem(o));
+			LaunchReq rq;
+			rq.opt = o, rq.d_order = (const int32_t*)tmp.p, rq.n_items = G.n, rq.slots = slots, rq.group = G;
+			rq.geom = to_mid ? GEOM_MID : geom, rq.copy = copy, rq.want_kind = want_kind, rq.window_hint = hint, rq.ring16_allowed = ring16_allowed;
+			// (a re-run whose forecast is clamped to the four-slot window asks for the report as the wide class's measuring launch does, as it always has: nothing reads
+			// the word after a re-run — finalize() looked at it before, and the next align's reset kernel zeroes it)
+			rq.report_wide = rq.geom == GEOM_CHOOSE && hint == kBandWide4Window;
+			if (rc == 0) rc = run_batch_kernel(g, b, rq, &ran);
 			if (rc == 0) rc = hipStreamSynchronize(g->stream) == hipSuccess ? 0 : -1;
 			if (rc) return -1;
 			for (int32_t i : ids) b->h_kind[i] = (int8_t)ran;
 			return 0;
 		};
 		// a band re-run on sequence copies: the class-3 pairs of the list ("alpha16") apart from the rest, on the 4-bit form of the same geometry
-		auto rerun = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast = false, int geom = 0) -> int {
-			if (want_kind != 2 || g->acgt_off_once || pl_low_mem(step0 ? opt_hi : b->opt)) return rerun1(ids, step0, want_kind, slots, use_forecast, geom, false);
+		auto rerun = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast = false, Geom geom = GEOM_CHOOSE, CopyForm copy = COPY_2BIT, bool ring16_allowed = true) -> int {
+			if (want_kind != 2 || copy == COPY_BYTES || pl_low_mem(step0 ? opt_hi : b->opt)) return rerun1(ids, step0, want_kind, slots, use_forecast, geom, copy, ring16_allowed);
 			std::vector<int32_t> nib_ids, rest;
 			for (int32_t i : ids) (nib_pair(i) ? nib_ids : rest).push_back(i);
-			if (rerun1(rest, step0, want_kind, slots, use_forecast, geom, false)) return -1;
-			return rerun1(nib_ids, step0, want_kind, slots, use_forecast, geom, true);
+			if (rerun1(rest, step0, want_kind, slots, use_forecast, geom, COPY_2BIT, ring16_allowed)) return -1;
+			return rerun1(nib_ids, step0, want_kind, slots, use_forecast, geom, COPY_NIB, ring16_allowed);
 		};
 		const int wide = 1 << 30;
 		for (int z = 0; z < 2; ++z) {
 			if (rerun(to_generic[z], z, 0, grid0)) return -1;
-			g->ring16_off_once = true;
-			const int rc32 = rerun(to_generic32[z], z, 0, grid0);
-			g->ring16_off_once = false;
-			if (rc32) return -1;
+			if (rerun(to_generic32[z], z, 0, grid0, false, GEOM_CHOOSE, COPY_2BIT, false)) return -1;
 			if (rerun(to_band_wide[z], z, 2, wide, true)) return -1;
-			if (rerun(to_band_span[z], z, 2, wide, false, 1024)) return -1;
-			g->acgt_off_once = true;
-			const int rc_bytes = rerun(to_band_bytes[z], z, 2, wide);
-			g->acgt_off_once = false;
-			if (rc_bytes) return -1;
+			if (rerun(to_band_span[z], z, 2, wide, false, GEOM_SPAN)) return -1;
+			if (rerun(to_band_bytes[z], z, 2, wide, false, GEOM_CHOOSE, COPY_BYTES)) return -1;
 			if (rerun(same_fewer[0][z], z, 0, std::max(1, std::min<int>(tb_slots, (int)same_fewer[0][z].size())))) return -1;
 			bool all_span = !same_fewer[2][z].empty();
-			for (int32_t i : same_fewer[2][z]) all_span = all_span && b->h_class[i] == 5;
-			if (rerun(same_fewer[2][z], z, 2, std::max(1, std::min<int>(tb_slots, (int)same_fewer[2][z].size())), false, all_span ? 1024 : 0)) return -1;
+			for (int32_t i : same_fewer[2][z]) all_span = all_span && b->h_class[i] == CLS_SPAN;
+			if (rerun(same_fewer[2][z], z, 2, std::max(1, std::min<int>(tb_slots, (int)same_fewer[2][z].size())), false, all_span ? GEOM_SPAN : GEOM_CHOOSE)) return -1;
 		}
 		if (fetch()) return -1;
 	}

@@ -1,4 +1,4 @@
-"""The packed band kernel's five- and six-slot copies of the 512-thread geometry on biased offsets — wfa_band2_kernel<512, 5 | 6, E1, E2, TB, 1, 1, FOLD>, class 14
+"""The packed band kernel's five- and six-slot copies of the 512-thread geometry on biased offsets — wfa_band2_kernel<512, 5 | 6, E1, E2, TB, 1, 1, FOLD>, class 14 (CLS_BIASED)
 of the host's routing — for every set but (2,1): (2,2) folded and not, (1,1), (3,1), (3,2), (4,1), built by miniwfa_amd/csrc/mwf_band2_bi.hip and
 mwf_band2_bi_deep.hip.  One entry each, with what reaches it and the inputs of its two test groups.
 
@@ -7,7 +7,7 @@ mwf_band2_bi_deep.hip.  One entry each, with what reaches it and the inputs of i
   tests/test_band_biased_gpu.py          the short end, default routing, the range check, gap runs, forced-routing fuzz, guard rails
 
 Built the way tests/band_deep_matrix.py is: a SECOND, private instance of band_matrix.py under another module name.  Its PEN gains the deep module's three sets,
-and its host_class — the restatement of mwf_plan.cpp's class rule — admits class 14 for the sets whose copies are built (band2_biased512_supported) where the
+and its host_class — the restatement of the class rule (mwf_plan_classes.h classify_pair) — admits class 14 for the sets whose copies are built (band2_biased512_supported) where the
 public one admits it for (2,1) alone.  `band_matrix` as every other test imports it and the deep module's instance are only read from."""
 from __future__ import annotations
 
@@ -38,7 +38,7 @@ def _private_band_matrix():
     mod.PEN = dict(mod.PEN, **DEEP_PEN)
 
     def host_class(p: dict, tl: int, ql: int, wide_slots: int = 0, band_span: int = 1) -> int:
-        """band_matrix.host_class with class 14 open to every set whose copies are built; the rule's form and order are mwf_plan.cpp's."""
+        """band_matrix.host_class with class 14 open to every set whose copies are built; the rule's form and order are classify_pair's (mwf_plan_classes.h)."""
         ln, bound = tl + ql, mod.penalty_bound(p, tl, ql)
         window = min(ln + 1, 2 * bound + 3)
         skew = abs(tl - ql)

@@ -51,7 +51,7 @@ def _src_const(name: str) -> int:
 
 FOLD_MAX_LAG = _src_const("kFoldMaxLag")   # o1 + e1 below it folds (launch_variant), from it on it must not
 BIAS_OVER, BIAS_MARGIN = _src_const("kBiasOver"), _src_const("kBiasMargin")
-SPAN_MAX_SEQ = 62000                       # mwf_plan.cpp kBandSpanMaxSeq
+SPAN_MAX_SEQ = 62000                       # mwf_plan_classes.h kBandSpanMaxSeq
 
 # ---- penalty sets -----------------------------------------------------------------------------------------------------------------------
 # (2,1): the defaults fold (o1 == x); the second set cannot.  (2,2): main.c's -a preset — on the default x, o1, e1 it is the same set as "o2=4, e2=2" —
@@ -100,7 +100,7 @@ def nwk(g: Geom) -> int:
 
 
 def admission_window(g: Geom) -> int:
-    """The widest window the planner chooses the geometry for: (waves x K chunks - 1) x 256 - 64 columns (mwf_plan.cpp:42-50, kBand*Window / band_span_window)."""
+    """The widest window the planner chooses the geometry for: (waves x K chunks - 1) x 256 - 64 columns (mwf_plan_classes.h: kBand*Window / band_window)."""
     return (nwk(g) - 1) * CHUNK - 64
 
 
@@ -256,14 +256,15 @@ def device_kernels(obj: str, kernel: str = "wfa_band2_kernel"):
 
 # ---- the host's rules, restated ---------------------------------------------------------------------------------------------------------
 def penalty_bound(p: dict, tl: int, ql: int) -> int:
-    """mwf_plan.cpp penalty_bound: delete the whole target, insert the whole query."""
+    """mwf_plan_classes.h penalty_bound: delete the whole target, insert the whole query."""
     gap = lambda L: 0 if L == 0 else min(p["o1"] + L * p["e1"], p["o2"] + L * p["e2"])
     return gap(tl) + gap(ql)
 
 
 def host_class(p: dict, tl: int, ql: int, wide_slots: int = 0, band_span: int = 1) -> int:
-    """The size class mwf_gpu_batch_align gives an A/C/G/T pair when the lane, mid and whole-device kernels are off and the divergence estimate is not
-    used (COMMON_DEFAULT_ROUTING): 4, 3, 2: the 64-, 128-, 256-thread geometries, 1: 512 threads, 14: its copies on biased offsets, 13: span, 0: generic."""
+    """The size class classify_pair (mwf_plan_classes.h) gives an A/C/G/T pair when the lane, mid and whole-device kernels are off and the divergence estimate is not
+    used (COMMON_DEFAULT_ROUTING), as its PairClass number: 4, 3, 2: CLS_MICRO, CLS_TINY, CLS_SMALL (the 64-, 128-, 256-thread geometries), 1: CLS_WIDE (512 threads),
+    14: CLS_BIASED (its copies on biased offsets), 13: CLS_SPAN, 0: CLS_GENERIC.  tests/test_plan_classes_cpu.py compares the two at every limit."""
     ln, bound = tl + ql, penalty_bound(p, tl, ql)
     window = min(ln + 1, 2 * bound + 3)
     skew = abs(tl - ql)
@@ -485,7 +486,7 @@ def _ladder_pair(g: Geom, pen_name: str, j: int):
     L = g.L
     if g.route in ("block", "wide4"):
         L = max(L, (span_columns(g) + CHUNK) * (5 if pen_name == "edit" else 4) // 4)
-        if g.route == "wide4":   # (plain 16-bit offsets: target length + worst-case penalty below 32767, mwf_plan.cpp `packable`)
+        if g.route == "wide4":   # (plain 16-bit offsets: target length + worst-case penalty below 32767, mwf_plan_classes.h classify_pair `packable`)
             p = PEN[pen_name]
             while L + penalty_bound(p, L, L + L // 50) >= 32767 - 64:
                 L -= 128

@@ -13,7 +13,7 @@ The generic kernel takes ANY penalties (reference: one loop, miniwfa.c:243-259, 
 not sized to "fit": the kernel finishes whatever it is given, and the only hand-backs it has are the 16-bit rows' (the edge tests).  What a cell's batch must
 satisfy is what makes the host launch exactly that form ONCE:
   block cells   force_kind 0 and block N (scalar cells: scalar_generic 1) keep the whole batch in one group — except that in low-memory mode a pair whose
-                penalty bound lies below `step` can never take a snapshot and runs in a high-memory launch of its own (mwf_plan.cpp classify, step0): the
+                penalty bound lies below `step` can never take a snapshot and runs in a high-memory launch of its own (mwf_plan_classes.h classify_pair, step0): the
                 low-memory batches hold the pairs with bound >= step only
   LDS2 cells    block 0, e2 == 1, no step, div_aware 0, and min(max(tl + ql) + 1, 2 max(bound) + 3) >= 8192 over the batch (run_batch_kernel): then 768 threads
                 on 32-bit rows (ring16 0), and on 16-bit rows (ring16 2) 512 threads score-only, 768 with traceback; every pair plain A/C/G/T

@@ -5,7 +5,7 @@ other fixtures are thin on — the ones in which round 5's fuzzers found bit-exa
   * unrelated pairs of 0.5 - 20 kb (windows that fill the matrix, many shrinks: miniwfa.c:139-171),
   * length-skewed pairs, tl / ql >= 4 either way, related and unrelated (the window's start climbs across chunk boundaries),
   * identical pairs and other long pairs to be run side by side in low-memory mode (checkpoints, miniwfa.c:413-416, 551-601),
-  * pairs that sit exactly on the length limits of the host's size classes (mwf_plan.cpp: mwf_gpu_batch_align / choose_kernel).
+  * pairs that sit exactly on the length limits of the host's size classes (mwf_plan_classes.h: classify_pair; mwf_plan.cpp: choose_kernel).
 
 Run in the build container:   python tests/golden/make_golden_blind.py
 Each line: a generator spec (miniwfa_amd.synth.spec_pair — no sequence text), the mwf_opt_t fields, the reference's (s, n_iter, CIGAR
@@ -102,7 +102,7 @@ def main():
                 sp = {"kind": "fit", "seed": nxt(), "tl": n, "ql": n + (j - 3) * 7, "p": (0.1, 0.03)[g]}
             add(f"side-by-side-{g}", sp, flag=1, step=step)
 
-    # ---- 4. pairs exactly on the size classes' length limits (mwf_plan.cpp): tl + ql + 1 == limit - 1, limit, limit + 1
+    # ---- 4. pairs exactly on the size classes' length limits (mwf_plan_classes.h classify_pair): tl + ql + 1 == limit - 1, limit, limit + 1
     for limit in (1400, 3600, 8200, 24576):
         for d in (-1, 0, 1):
             total = limit + d - 1               # tl + ql

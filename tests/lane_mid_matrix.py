@@ -9,7 +9,7 @@ and the inputs of its two test groups, sized on the CPU from the oracle alone.  
 
 Rule: an instantiation is added (or removed, or re-parameterised) together with its entry here.
 
-fit = the host starts the pair on the kernel (lane_admits / mid_admits restate mwf_plan.cpp's classify) AND none of the kernel's documented hand-backs
+fit = the host starts the pair on the kernel (lane_admits / mid_admits restate mwf_plan_classes.h's classify_pair) AND none of the kernel's documented hand-backs
 fires, each restated on the oracle's band trace (Oracle.band_trace_far) and the pair's lengths — never on what the device did:
   lane  chunks    k_use >= lane_chunks on center = tl + 1 (mwf_lane.hip, the test in front of the penalty's chunks); exact
         shrink    a final penalty above 255 - nH: the kernel hands back at the first penalty whose good bits a shrink would read; exact
@@ -110,7 +110,7 @@ assert nH(PEN_BEYOND["lane_97"]) + 6 == 97 and nH(PEN_BEYOND["mid_nH65"]) == 65
 # Cell: kernel, instantiation, lane_chunks (0: mid), runs ((penalty set, band_fold) — each must launch exactly that instantiation)
 Cell = namedtuple("Cell", "kernel inst chunks runs")
 LANE_MAX_LEN = 325      # mwf_engine.h lane_max_len
-LANE_MAX_SKEW = 24      # classify: skew <= 24
+LANE_MAX_SKEW = 24      # classify_pair: skew <= 24
 LANE_S2_MIN_LEN = 450   # choose_kernel: 2-bit copies from 450 bases of target + query on
 LANE_COMMON = (("mid_max_pairs", 0), ("div_aware", 0), ("coop_min_len", 1 << 40))
 MID_COMMON = (("lane_max_len", 0), ("div_aware", 0), ("coop_min_len", 1 << 40))
@@ -195,7 +195,7 @@ def object_instantiations(kernel: str):
     return out
 
 
-# ---- the host's rules, restated (mwf_plan.cpp mwf_gpu_batch_align: classify, and choose_kernel) ------------------------------------------
+# ---- the host's rules, restated (mwf_plan_classes.h classify_pair, and mwf_plan.cpp choose_kernel) ------------------------------------------
 def _lenw(tl: int, ql: int) -> int:
     """The pair's length as the class limits see it (div_aware 0): a forced gap counts six-fold beyond a sixteenth of the length."""
     ln, skew = tl + ql, abs(tl - ql)
@@ -252,7 +252,7 @@ def _mid_groups(p: dict, window: int, seq_bytes: int) -> int:
 
 
 def mid_groups(p: dict, pairs) -> int:
-    """choose_kernel (geom_block 33): the span of a LAUNCH, from the longest pair, the largest penalty bound and the largest sequence copy of its pairs."""
+    """choose_kernel (GEOM_MID): the span of a LAUNCH, from the longest pair, the largest penalty bound and the largest sequence copy of its pairs."""
     max_len = max(len(t) + len(q) for t, q in pairs)
     max_bound = max(penalty_bound(p, len(t), len(q)) for t, q in pairs)
     g = _mid_groups(p, min(max_len + 1, 2 * max_bound + 3), _group_seq_lds(pairs))
@@ -272,7 +272,7 @@ def mid_span(groups: int, tl: int, ql: int):
 
 
 def mid_admits(p: dict, tl: int, ql: int):
-    """classify, class 11: False, or "holds_all" / "want" — which of the two conditions admitted the pair.  (The band class the lengths give must be
+    """classify_pair, CLS_MID: False, or "holds_all" / "want" — which of the two conditions admitted the pair.  (The band class the lengths give must be
     at most 4: true of every pair whose weighed length stays within 8200.)"""
     bound, ln = penalty_bound(p, tl, ql), tl + ql
     if not mid_supported(p) or tl + bound >= 32760 or _lenw(tl, ql) + 1 > 8200:
