@@ -3,6 +3,8 @@
 // 3 and 4).  The description of the kernel is at the top of mwf_sys.hip.  Everything here has internal linkage: a unit gets the forms it launches.
 #pragma once
 #include <atomic>
+#include <cstdio>
+#include <cstdlib>
 #include "mwf_device.h"
 
 namespace mwf {
@@ -1198,7 +1200,7 @@ int launch_pass_pc(const BatchArgs &a, int grid, hipStream_t st)
 {
 	const void *fn;
 	if (a.coop_pass == 3) {
-		if constexpr (TB) return -1;
+		if constexpr (TB || DEFER) return -1; // (launch_pass_d sends the provenance pass to the plain form: no deferred provenance kernel is built)
 		else fn = reinterpret_cast<const void*>(&wfa_sys_seg_kernel<E1, E2, P, DEFER, C>);
 	} else fn = reinterpret_cast<const void*>(&wfa_sys_kernel<E1, E2, P, DEFER, TB, C>);
 	// the form about to be launched must fit a CU (registers, LDS, scratch): asked once per form (the library is built for one device model)
@@ -1211,6 +1213,11 @@ int launch_pass_pc(const BatchArgs &a, int grid, hipStream_t st)
 		known.store(ok ? 1 : 2, std::memory_order_relaxed);
 	}
 	if (known.load(std::memory_order_relaxed) != 1) return kSysNotResident;
+	// diagnostics: which instantiation this launch is — the template arguments, as tests/sys_matrix.py lists them (SEG 1: wfa_sys_seg_kernel,
+	// whose arguments are E1, E2, P, DEFER, C) —, the pass, and the pairs side by side x the workgroups each of them has
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] sys launch: E1 %d E2 %d P %d DEFER %d TB %d C %d SEG %d, pass %d, groups %d x %d, grid %d\n", E1, E2, P, (int)DEFER, (int)TB, C,
+		        (int)(a.coop_pass == 3), (int)a.coop_pass, (int)a.coop_groups, (int)a.coop_group_size, grid);
 	BatchArgs arg = a;
 	void *args[] = {(void*)&arg};
 	if (a.sys_coop_launch) {
@@ -1241,7 +1248,8 @@ int launch_pass_p(const BatchArgs &a, int grid, hipStream_t st)
 #ifdef MWF_SYS_C2 // (experiment: 128-column slots that own 112)
 	if (a.sys_c == 2) return launch_pass_c<E1, E2, DEFER, TB, 2>(a, grid, st);
 #endif
-	return launch_pass_c<E1, E2, DEFER, TB, 4>(a, grid, st);
+	if constexpr (DEFER && TB) return -1; // (launch_pass_d sends the traceback pass on four columns per lane to the plain form: the deferred one is built for one column only)
+	else return launch_pass_c<E1, E2, DEFER, TB, 4>(a, grid, st);
 }
 
 // DEFER needs every H lag >= 3 (the edit-distance preset, every lag 1, only ever takes the plain form)
