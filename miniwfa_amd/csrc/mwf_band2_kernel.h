@@ -79,8 +79,6 @@ constexpr uint32_t kNibTag = 0x40; // high nibble of an image byte (MWF_ALPHA16_
 constexpr bool band2_geo_cached(int T, int K, bool TB) { return kTabProbe && T == 512 && (K == 3 || (K == 4 && !TB)); }
 constexpr int kTabSlack = 258; // table entries beyond tl + ql: target position tl, query position -1, and the query positions a chunk's columns beyond cmax clamp to (up to ql + 255)
 
-__device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
 __device__ __forceinline__ int32_t lo16(int32_t v) { return (int32_t)(int16_t)(v & 0xffff); }
 __device__ __forceinline__ int32_t hi16(int32_t v) { return v >> 16; }
 __device__ __forceinline__ int32_t pack2(int32_t a, int32_t b)
@@ -89,7 +87,6 @@ __device__ __forceinline__ int32_t pack2(int32_t a, int32_t b)
 	const short2_t v = __builtin_amdgcn_cvt_pk_i16(a, b); // saturating
 	return __builtin_bit_cast(int32_t, v);
 }
-__device__ __forceinline__ int32_t both16(int32_t v) { return (int32_t)(((uint32_t)v << 16) | ((uint32_t)v & 0xffffu)); }
 
 // four bytes at byte offset `off` of the sequence copy (which starts at LDS offset 0)
 __device__ __forceinline__ uint32_t seq4(int32_t off)
@@ -276,11 +273,6 @@ __device__ __forceinline__ void build_probe_table(int32_t tl, int32_t ql, int32_
 	}
 }
 
-__device__ __forceinline__ uint32_t inm_bit(int32_t d, int32_t k, int32_t tl, int32_t ql)
-{
-	return (uint32_t)((uint32_t)(k + 1) < (uint32_t)(tl + 1)) & (uint32_t)((uint32_t)(d + k + 1) < (uint32_t)(ql + 1));
-}
-
 __device__ __forceinline__ unsigned long long lane_mask(int32_t base, int32_t k, int32_t a, int32_t b)
 {
 	int32_t lmin = a - base - k, lmax = b - base - k;
@@ -336,37 +328,12 @@ struct alignas(16) Band2Lds {
 	int32_t dump[64 * 2 + (2 * NWK + 4) * 4]; // where the lanes that do not hold an outer column put theirs (no exec-mask games around the stores)
 };
 
-// ---- packed 16-bit arithmetic: two columns per register, every operation one VOP3P instruction
+// ---- packed 16-bit arithmetic: two columns per register, every operation one VOP3P instruction.  Offsets are SIGNED halves here; what works on
+// unsigned halves (pk_minu, pk_subsat, pk_nonzero_mask, pk_ne1, pk_mad) is shared with the generic kernel: mwf_device.h
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-#define MWF_BC(T, v) __builtin_bit_cast(T, v)
 __device__ __forceinline__ int32_t pk_max(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_max(MWF_BC(s16x2, a), MWF_BC(s16x2, b))); }
 __device__ __forceinline__ int32_t pk_add(int32_t a, int32_t b) { return MWF_BC(int32_t, (s16x2)(MWF_BC(s16x2, a) + MWF_BC(s16x2, b))); }
 __device__ __forceinline__ int32_t pk_sub(int32_t a, int32_t b) { return MWF_BC(int32_t, (s16x2)(MWF_BC(s16x2, a) - MWF_BC(s16x2, b))); }
-__device__ __forceinline__ int32_t pk_minu(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_min(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
-// max(a - b, 0) on unsigned halves (v_pk_sub_u16 clamp): zero iff a <= b
-__device__ __forceinline__ int32_t pk_subsat(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_sub_sat(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
-// 0xffff in every half of x that is not zero (asm: the compiler turns the min into compares, selects and a v_perm)
-__device__ __forceinline__ int32_t pk_nonzero_mask(int32_t x)
-{
-	int32_t m;
-	asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]\n\tv_pk_sub_i16 %0, 0, %0 op_sel_hi:[0,1]" : "=&v"(m) : "v"(x));
-	return m;
-}
-// 1 in every half where a != b
-__device__ __forceinline__ int32_t pk_ne1(int32_t a, int32_t b)
-{
-	int32_t m;
-	asm("v_xor_b32 %0, %1, %2\n\tv_pk_min_u16 %0, %0, 1 op_sel_hi:[1,0]" : "=&v"(m) : "v"(a), "v"(b));
-	return m;
-}
-// a * b + c on unsigned halves
-__device__ __forceinline__ int32_t pk_mad(int32_t a, int32_t b, int32_t c)
-{
-	int32_t m;
-	asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c));
-	return m;
-}
 __device__ __forceinline__ int32_t bfi(int32_t mask, int32_t a, int32_t b) { return (a & mask) | (b & ~mask); } // mask ? a : b, bitwise
 __device__ __forceinline__ int32_t half_of(int32_t v, int hi) { return hi ? v >> 16 : (int32_t)(int16_t)(v & 0xffff); }
 __device__ __forceinline__ int32_t pair_of(int32_t lo, int32_t hi) { return (int32_t)(((uint32_t)hi << 16) | ((uint32_t)lo & 0xffffu)); }

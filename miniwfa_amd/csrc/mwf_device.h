@@ -1,6 +1,7 @@
 // mwf_device.h — device-side helpers shared by every alignment kernel (mwf_kernels.hip generic, mwf_band2_kernel.h packed band,
 // mwf_lane.hip short pairs, mwf_mid.hip mid-size pairs of small batches, mwf_sys.hip whole device): the recurrence and its
-// traceback byte, kernel-argument access, the shared traceback, per-pair memory views and outputs.
+// traceback byte, kernel-argument access, the shared traceback, per-pair memory views and outputs, and the lane-shift and packed 16-bit
+// helpers of the kernels whose lanes own four columns (generic stream passes, whole-device pass, packed band) — each defined here once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -278,6 +279,57 @@ struct PairMem {
 	// the bytes at ts / qs (which may themselves point into LDS)
 	const uint8_t *t2, *q2;
 };
+
+// ---- helpers of the kernels whose lanes own four consecutive columns (mwf_kernels.hip stream passes, mwf_sys_pass.h, mwf_band2_kernel.h) ----
+// the value of the lane to the left / right (a DPP wave shift); lane 0 / lane 63 get `fill`
+__device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
+// in_matrix as a 0/1 word (no short-circuit: straight-line code)
+__device__ __forceinline__ uint32_t inm_bit(int32_t d, int32_t k, int32_t tl, int32_t ql)
+{
+	return (uint32_t)((uint32_t)(k + 1) < (uint32_t)(tl + 1)) & (uint32_t)((uint32_t)(d + k + 1) < (uint32_t)(ql + 1));
+}
+__device__ __forceinline__ int32_t pick4(int32_t i, int32_t a0, int32_t a1, int32_t a2, int32_t a3)
+{
+	return i == 0 ? a0 : i == 1 ? a1 : i == 2 ? a2 : a3;
+}
+// first probe of the match extension on the byte sequences in global memory: four bases, zero where they agree
+__device__ __forceinline__ uint32_t probe4g(const PairMem &M, int32_t j, int32_t i)
+{
+	uint32_t a, b;
+	__builtin_memcpy(&a, M.ts + j, 4);
+	__builtin_memcpy(&b, M.qs + i, 4);
+	return a ^ b;
+}
+__device__ __forceinline__ int32_t both16(int32_t v) { return (int32_t)(((uint32_t)v << 16) | ((uint32_t)v & 0xffffu)); }
+// packed 16-bit arithmetic on UNSIGNED halves (two columns per register, one VOP3P instruction each); what is signed in one kernel and
+// unsigned in another (add, sub, max) stays with its kernel under a name of its own
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+#define MWF_BC(T, v) __builtin_bit_cast(T, v)
+__device__ __forceinline__ int32_t pk_minu(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_min(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
+// max(a - b, 0) (v_pk_sub_u16 clamp): zero iff a <= b
+__device__ __forceinline__ int32_t pk_subsat(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_sub_sat(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
+// 0xffff in every half of x that is not zero (asm: the compiler turns the min into compares, selects and a v_perm)
+__device__ __forceinline__ int32_t pk_nonzero_mask(int32_t x)
+{
+	int32_t m;
+	asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]\n\tv_pk_sub_i16 %0, 0, %0 op_sel_hi:[0,1]" : "=&v"(m) : "v"(x));
+	return m;
+}
+// 1 in every half where a != b
+__device__ __forceinline__ int32_t pk_ne1(int32_t a, int32_t b)
+{
+	int32_t m;
+	asm("v_xor_b32 %0, %1, %2\n\tv_pk_min_u16 %0, %0, 1 op_sel_hi:[1,0]" : "=&v"(m) : "v"(a), "v"(b));
+	return m;
+}
+// a * b + c
+__device__ __forceinline__ int32_t pk_mad(int32_t a, int32_t b, int32_t c)
+{
+	int32_t m;
+	asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c));
+	return m;
+}
 
 // the traceback byte of (penalty row + 1, column col)
 __device__ __forceinline__ uint32_t tb_byte(const PairMem &M, int32_t row, int32_t col)

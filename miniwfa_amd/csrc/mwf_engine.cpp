@@ -3,7 +3,7 @@
 //
 // Boundary: the reference's device-free API mwf_wfa_exact/auto/chain
 // (miniwfa.c:603-615, :850-908) is kept; a call ships its pair(s) to HBM, runs the kernels of
-// mwf_kernels.hip / mwf_band2.hip / mwf_lane.hip / mwf_mid.hip / mwf_sys.hip and copies back (s, n_iter, n_cigar, CIGAR).  r->cigar is
+// mwf_kernels.hip / mwf_band2.hip / mwf_lane.hip / mwf_mid.hip / mwf_sys.hip (reset and sketches: mwf_sketch.hip) and copies back (s, n_iter, n_cigar, CIGAR).  r->cigar is
 // allocated from the caller's kalloc arena exactly as the reference does (miniwfa.c:434).  kalloc arenas for
 // scratch are replaced by device pools that only ever grow:
 //   * one workspace per engine (ring, traceback arena, row table, CIGAR scratch, snapshots);

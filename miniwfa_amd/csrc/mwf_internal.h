@@ -138,9 +138,10 @@ struct BatchArgs {
 	int32_t band_lds_tab;      // packed band kernel, table form (mwf_band2_tab.hip): bytes of the probe table in front of the sequence copy (part of band_lds_seq)
 };
 
-// launch wrappers implemented in mwf_kernels.hip (generic kernel: any penalties, any band, low-memory mode)
-int launch_reset(int32_t *status, int32_t *s, int32_t n, unsigned long long *cig_head, int32_t *queue, int32_t n_queue, void *stream);
+// launch wrapper implemented in mwf_kernels.hip (generic kernel: any penalties, any band, low-memory mode)
 int launch_batch(const BatchArgs &a, int grid, int block, void *stream);
+// mwf_sketch.hip: the reset at the start of an align call and the 8-mer sketches
+int launch_reset(int32_t *status, int32_t *s, int32_t n, unsigned long long *cig_head, int32_t *queue, int32_t n_queue, void *stream);
 // 8-mer sketch of `samples` (<= 16) pairs of a device-resident batch: out[k] = 8-mers of pair (k n / samples)'s query prefix that occur in its target prefix
 int launch_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, int32_t n, int32_t samples, int32_t *out, void *stream);
 // the same statistic over the WHOLE sequences of every pair order[0 .. n) (order null: pairs 0 .. n; one workgroup each): out[k] = 8-mers of that pair's query that occur

@@ -1,4 +1,6 @@
-// mwf_kernels.hip — gfx950 kernels for the exact WFA score-and-CIGAR path.
+// mwf_kernels.hip — the generic gfx950 kernel for the exact WFA score-and-CIGAR path (any penalties, any window; every hand-back of the
+// other kernels ends here): the two passes, the per-pair driver, the 14 + 1 instantiations and — at the end, listed once — their launch
+// and occupancy (with_generic_form).  The reset and sketch kernels that used to live here: mwf_sketch.hip.
 //
 // What the reference does on one CPU thread per pair (miniwfa.c:380-435 core loop, :551-601
 // low-memory first pass, :329-377 traceback) is restated here for a wave64 machine:
@@ -40,9 +42,6 @@ using namespace dev;
 
 namespace {
 
-// Flatten the shadow ring into the next snapshot and renumber it (reference wf_snapshot1, miniwfa.c:451-474).
-// Snapshot record in snap_meta, stride 4+4*NS ints: [arena offset lo, hi, penalty, n] then per array-slice
-// [penalty of the slice, first column, width, first index].  Array-slices are listed H slots, then E1, F1, E2, F2.
 template <typename ArgsT>
 __device__ __forceinline__ Penalty load_penalty(const ArgsT &A)
 {
@@ -52,6 +51,9 @@ __device__ __forceinline__ Penalty load_penalty(const ArgsT &A)
 	return P;
 }
 
+// Flatten the shadow ring into the next snapshot and renumber it (reference wf_snapshot1, miniwfa.c:451-474).
+// Snapshot record in snap_meta, stride 4+4*NS ints: [arena offset lo, hi, penalty, n] then per array-slice
+// [penalty of the slice, first column, width, first index].  Array-slices are listed H slots, then E1, F1, E2, F2.
 template <int T, typename ArgsT, typename ShT>
 __device__ bool take_snapshot(const ArgsT &A, const PairMem &M, ShT &sh, int32_t n_snap, int64_t &snap_used,
                               int32_t s, int32_t curH, int32_t cur1, int32_t cur2)
@@ -337,53 +339,21 @@ __device__ PassResult forward_pass(const ArgsT &A, const PairMem &M, ShT &sh, in
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same pass with four columns per lane (the band kernel's inner code, mwf_band.hip) for every mode except the
-// low-memory first pass.  forward_pass above moves 9 dwords in and 5 out per lane per cell; here a lane owns four
+// The same pass with four columns per lane (the packed band kernel's layout, mwf_band2_kernel.h) for every mode, the
+// low-memory first pass included.  forward_pass above moves 9 dwords in and 5 out per lane per cell; here a lane owns four
 // consecutive columns of a 256-column chunk (chunk g belongs to wave g mod waves), so each array-slice is ONE 16-byte
-// load or store per lane, the d-1 / d+1 neighbours come from the adjacent lane through a DPP wave shift and only
-// lanes 0 and 63 load a neighbouring chunk's outer column.  Same 48 algorithmic bytes per cell, a quarter of the
-// memory instructions, four times the bytes in flight per wave.
-__device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
-
-__device__ __forceinline__ uint32_t probe4g(const PairMem &M, int32_t j, int32_t i)
-{
-	uint32_t a, b;
-	__builtin_memcpy(&a, M.ts + j, 4);
-	__builtin_memcpy(&b, M.qs + i, 4);
-	return a ^ b;
-}
+// load or store per lane, the d-1 / d+1 neighbours come from the adjacent lane through a DPP wave shift (dev::from_left /
+// from_right) and only lanes 0 and 63 load a neighbouring chunk's outer column.  Same 48 algorithmic bytes per cell, a
+// quarter of the memory instructions, four times the bytes in flight per wave.
 
 #ifndef MWF_H16_RELAX
 #define MWF_H16_RELAX 1 // 16-bit-ring kernel: the last chunk's stores may cross the per-penalty barrier (0: drain everything)
 #endif
-// ---- packed 16-bit arithmetic on the codes of the 16-bit ring rows (two columns per register, one VOP3P instruction each)
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-#define MWF_BC(T, v) __builtin_bit_cast(T, v)
+// ---- packed 16-bit arithmetic on the codes of the 16-bit ring rows (two columns per register, one VOP3P instruction each).  Codes are UNSIGNED
+// halves: max, add and sub here (the packed band kernel has signed ones under the plain names); pk_minu, pk_subsat, pk_mad, pk_ne1, pk_nonzero_mask: mwf_device.h
 __device__ __forceinline__ int32_t pk_maxu(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_max(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
-__device__ __forceinline__ int32_t pk_minu(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_min(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); }
-__device__ __forceinline__ int32_t pk_add(int32_t a, int32_t b) { return MWF_BC(int32_t, (u16x2)(MWF_BC(u16x2, a) + MWF_BC(u16x2, b))); }
-__device__ __forceinline__ int32_t pk_sub(int32_t a, int32_t b) { return MWF_BC(int32_t, (u16x2)(MWF_BC(u16x2, a) - MWF_BC(u16x2, b))); }
-__device__ __forceinline__ int32_t pk_subsat(int32_t a, int32_t b) { return MWF_BC(int32_t, __builtin_elementwise_sub_sat(MWF_BC(u16x2, a), MWF_BC(u16x2, b))); } // max(a - b, 0)
-__device__ __forceinline__ int32_t pk_mad(int32_t a, int32_t b, int32_t c)
-{
-	int32_t m;
-	asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c));
-	return m;
-}
-__device__ __forceinline__ int32_t pk_ne1(int32_t a, int32_t b) // 1 in every half where a != b
-{
-	int32_t m;
-	asm("v_xor_b32 %0, %1, %2\n\tv_pk_min_u16 %0, %0, 1 op_sel_hi:[1,0]" : "=&v"(m) : "v"(a), "v"(b));
-	return m;
-}
-__device__ __forceinline__ int32_t pk_nonzero_mask(int32_t x) // 0xffff in every half of x that is not zero
-{
-	int32_t m;
-	asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]\n\tv_pk_sub_i16 %0, 0, %0 op_sel_hi:[0,1]" : "=&v"(m) : "v"(x));
-	return m;
-}
-__device__ __forceinline__ int32_t both16(int32_t v) { return (int32_t)(((uint32_t)v << 16) | ((uint32_t)v & 0xffffu)); }
+__device__ __forceinline__ int32_t pk_addu(int32_t a, int32_t b) { return MWF_BC(int32_t, (u16x2)(MWF_BC(u16x2, a) + MWF_BC(u16x2, b))); }
+__device__ __forceinline__ int32_t pk_subu(int32_t a, int32_t b) { return MWF_BC(int32_t, (u16x2)(MWF_BC(u16x2, a) - MWF_BC(u16x2, b))); }
 // code + 1 for a live code (>= 2), 0 for a dead one (0, or the 1 a dead code picked up): the collapse of what outlives a penalty
 __device__ __forceinline__ int32_t pk_live_inc(int32_t x)
 {
@@ -420,16 +390,6 @@ __device__ __forceinline__ uint32_t pack2bit_global(const uint8_t *src, int32_t 
 		dst[w] = out;
 	}
 	return bad;
-}
-
-__device__ __forceinline__ uint32_t inm_bit(int32_t d, int32_t k, int32_t tl, int32_t ql)
-{
-	return (uint32_t)((uint32_t)(k + 1) < (uint32_t)(tl + 1)) & (uint32_t)((uint32_t)(d + k + 1) < (uint32_t)(ql + 1));
-}
-
-__device__ __forceinline__ int32_t pick4(int32_t i, int32_t a0, int32_t a1, int32_t a2, int32_t a3)
-{
-	return i == 0 ? a0 : i == 1 ? a1 : i == 2 ? a2 : a3;
 }
 
 // lanes l of interleaved good word k (column = base + 4*l + k) whose column lies in [a,b]
@@ -671,13 +631,13 @@ __device__ PassResult stream_pass(const ArgsT &A, const PairMem &M, Shared &sh, 
 				if (LDS2 && prev_in_lds) vg2 = lane == 0 ? e2_edge[epar ^ 1][(g - 1) & 63][1] : e2_edge[epar ^ 1][(g + 1) & 63][0];
 				else vg2 = ld1(lane == 0 ? sE2 : sF2, ce);
 				// local columns of the two registers' halves: x = (4l, 4l+1), y = (4l+2, 4l+3)
-				const int32_t RX = (int32_t)((uint32_t)(4 * lane) | (uint32_t)(4 * lane + 1) << 16), RY = pk_add(RX, TWO);
+				const int32_t RX = (int32_t)((uint32_t)(4 * lane) | (uint32_t)(4 * lane + 1) << 16), RY = pk_addu(RX, TWO);
 				int32_t outx = 0, outy = 0; // 0xffff in the halves of columns outside [lo, hi]
 				if (!inner) { // reads outside a source window yield dead (what the reference's pads supply, miniwfa.c:96-99): dead is 0, so a mask is an AND
 					auto out_of = [&](int32_t wlo, int32_t whi, int32_t &mx, int32_t &my) { // halves of the columns outside [wlo, whi]
 						const int32_t lo_r = both16(min(max(wlo - cb, 0), 256)), hi_r1 = both16(min(max(whi - cb + 1, 0), 256));
-						mx = pk_nonzero_mask(pk_subsat(lo_r, RX) | pk_subsat(pk_add(RX, ONE), hi_r1));
-						my = pk_nonzero_mask(pk_subsat(lo_r, RY) | pk_subsat(pk_add(RY, ONE), hi_r1));
+						mx = pk_nonzero_mask(pk_subsat(lo_r, RX) | pk_subsat(pk_addu(RX, ONE), hi_r1));
+						my = pk_nonzero_mask(pk_subsat(lo_r, RY) | pk_subsat(pk_addu(RY, ONE), hi_r1));
 					};
 					int32_t mx, my;
 					out_of(xlo, xhi, mx, my), HXx &= ~mx, HXy &= ~my;
@@ -746,18 +706,18 @@ __device__ PassResult stream_pass(const ArgsT &A, const PairMem &M, Shared &sh, 
 				// ---- lane geometry: j = k + 1 = code - 2 may reach rj = min(tl, ql - d); query index = j + d, d = c - 1 - tl (mod 2^16: the true value fits)
 				const int32_t x0 = min(cmax - c0, 65535), d0 = c0 - 1 - tl;
 				const int32_t Xx = (int32_t)(((uint32_t)x0 & 0xffffu) | (uint32_t)(x0 - 1) << 16), TLp = both16(tl);
-				const int32_t rjx = pk_minu(Xx, TLp), rjy = pk_minu(pk_sub(Xx, TWO), TLp);
-				const int32_t Dx = (int32_t)(((uint32_t)d0 & 0xffffu) | (uint32_t)(d0 + 1) << 16), Dy = pk_add(Dx, TWO);
+				const int32_t rjx = pk_minu(Xx, TLp), rjy = pk_minu(pk_subu(Xx, TWO), TLp);
+				const int32_t Dx = (int32_t)(((uint32_t)d0 & 0xffffu) | (uint32_t)(d0 + 1) << 16), Dy = pk_addu(Dx, TWO);
 				uint32_t gbits = 0;
 				if (track_good) { // some array holds an in-matrix offset (miniwfa.c:139-142) <=> j <= rj for a live code (dead: j wraps to 65534)
-					auto bad = [&](int32_t v, int32_t rj) { return pk_subsat(pk_sub(v, TWO), rj); }; // zero iff good
+					auto bad = [&](int32_t v, int32_t rj) { return pk_subsat(pk_subu(v, TWO), rj); }; // zero iff good
 					const int32_t bx = pk_minu(pk_minu(bad(hx_, rjx), pk_minu(bad(e1x, rjx), bad(f1x, rjx))), pk_minu(bad(e2x, rjx), bad(f2x, rjx))) | outx;
 					const int32_t by = pk_minu(pk_minu(bad(hy_, rjy), pk_minu(bad(e1y, rjy), bad(f1y, rjy))), pk_minu(bad(e2y, rjy), bad(f2y, rjy))) | outy;
 					gbits = (uint32_t)((bx & 0xffff) == 0) | (uint32_t)(((uint32_t)bx >> 16) == 0) << 1 | (uint32_t)((by & 0xffff) == 0) << 2 | (uint32_t)(((uint32_t)by >> 16) == 0) << 3;
 				}
 				// ---- match extension, first probe (sixteen bases of the 2-bit copies): j clamped to rj makes room = rj - j zero for dead and phantom offsets
-				const int32_t jx_ = pk_minu(pk_sub(hx_, TWO), rjx), jy_ = pk_minu(pk_sub(hy_, TWO), rjy);
-				const int32_t iqx = pk_add(jx_, Dx), iqy = pk_add(jy_, Dy);
+				const int32_t jx_ = pk_minu(pk_subu(hx_, TWO), rjx), jy_ = pk_minu(pk_subu(hy_, TWO), rjy);
+				const int32_t iqx = pk_addu(jx_, Dx), iqy = pk_addu(jy_, Dy);
 				uint32_t cnt[4];
 #pragma unroll
 				for (int u = 0; u < 4; ++u) {
@@ -769,7 +729,7 @@ __device__ PassResult stream_pass(const ArgsT &A, const PairMem &M, Shared &sh, 
 				typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 				const int32_t cx = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16(cnt[0], cnt[1])), cy = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16(cnt[2], cnt[3])); // saturating
 				const int32_t FULLp = both16(16);
-				const int32_t m9x = pk_minu(cx, pk_sub(rjx, jx_)), m9y = pk_minu(cy, pk_sub(rjy, jy_)); // > 16: the whole probe matched, room left
+				const int32_t m9x = pk_minu(cx, pk_subu(rjx, jx_)), m9y = pk_minu(cy, pk_subu(rjy, jy_)); // > 16: the whole probe matched, room left
 				int32_t nmx = pk_minu(m9x, FULLp), nmy = pk_minu(m9y, FULLp);
 				const int32_t pendp = pk_subsat(m9x, FULLp) | pk_subsat(m9y, FULLp);
 				if (__ballot(pendp != 0)) { // a run of >= 16 matches continues: its lane walks it 8 bytes per trip for four trips, then the whole wave does
@@ -807,7 +767,7 @@ __device__ PassResult stream_pass(const ArgsT &A, const PairMem &M, Shared &sh, 
 					}
 					nmx = (int32_t)(((uint32_t)nmat[0] & 0xffffu) | (uint32_t)nmat[1] << 16), nmy = (int32_t)(((uint32_t)nmat[2] & 0xffffu) | (uint32_t)nmat[3] << 16);
 				}
-				const int32_t hxx = pk_add(hx_, nmx), hxy = pk_add(hy_, nmy); // extended
+				const int32_t hxx = pk_addu(hx_, nmx), hxy = pk_addu(hy_, nmy); // extended
 				// termination test of the extension sweep (miniwfa.c:405-409): only column ql+1 can hold the end cell
 				uint32_t fin = 0;
 				int32_t done_info = 0;
@@ -1092,9 +1052,11 @@ __device__ PassResult stream_pass(const ArgsT &A, const PairMem &M, Shared &sh, 
 // STREAM: the four-columns-per-lane passes (two kernels rather than one, so that neither pays for the other's registers)
 // MODE: -1 score or traceback by A.want_cigar (one kernel for both); 0 / 1: a kernel for score-only / traceback alone, so that
 // neither pays for the other's registers (the kernels with E2/F2 in LDS, whose workgroups share a CU)
-template <int T, bool STREAM, bool LDS2, bool H16, int MODE, typename ArgsT>
-__device__ void align_pair(const ArgsT &A, Shared &sh, int32_t slot, int32_t pair)
+// ShT: dev::Shared, or dev::SharedBig (the window table of the big-ring kernel: one-column-per-lane passes only)
+template <int T, bool STREAM, bool LDS2, bool H16, int MODE, typename ArgsT, typename ShT>
+__device__ void align_pair(const ArgsT &A, ShT &sh, int32_t slot, int32_t pair)
 {
+	static_assert(STREAM || !(LDS2 || H16 || MODE >= 0), "only the stream passes have the LDS2 / H16 / single-mode forms");
 	PairMem M;
 	pair_mem(A, slot, pair, M);
 	const bool trace = A.dbg && pair == A.debug_pair;
@@ -1118,8 +1080,8 @@ __device__ void align_pair(const ArgsT &A, Shared &sh, int32_t slot, int32_t pai
 	}
 	if (status == ST_OK) {
 		if constexpr (STREAM && LDS2 && MODE >= 0) R = stream_pass<T, MODE == 1, LDS2, false, LDS2 && H16>(A, M, sh, MODE == 1 ? n_seg : 0, trace);
-		else if (STREAM && LDS2 && H16) R = A.want_cigar ? stream_pass<T, true, LDS2, false, LDS2 && H16>(A, M, sh, n_seg, trace) : stream_pass<T, false, LDS2, false, LDS2 && H16>(A, M, sh, 0, trace);
-		else if (STREAM) R = A.want_cigar ? stream_pass<T, true, LDS2>(A, M, sh, n_seg, trace) : stream_pass<T, false, LDS2>(A, M, sh, 0, trace);
+		else if constexpr (STREAM && LDS2 && H16) R = A.want_cigar ? stream_pass<T, true, LDS2, false, LDS2 && H16>(A, M, sh, n_seg, trace) : stream_pass<T, false, LDS2, false, LDS2 && H16>(A, M, sh, 0, trace);
+		else if constexpr (STREAM) R = A.want_cigar ? stream_pass<T, true, LDS2>(A, M, sh, n_seg, trace) : stream_pass<T, false, LDS2>(A, M, sh, 0, trace);
 		else R = A.want_cigar ? forward_pass<T, true, false>(A, M, sh, n_seg, trace) : forward_pass<T, false, false>(A, M, sh, 0, trace);
 		status = R.status;
 	}
@@ -1162,137 +1124,49 @@ __global__ __launch_bounds__(T, 1) void wfa_bigring_kernel(const BatchArgs)
 		__syncthreads();
 		if (item >= A.n_pairs) break;
 		const int32_t pair = A.order ? A.order[item] : item;
-		const int32_t slot = (int32_t)blockIdx.x;
-		PairMem M;
-		pair_mem(A, slot, pair, M);
-		const bool trace = A.dbg && pair == A.debug_pair;
-		int32_t n_seg = 0, status = ST_OK;
-		int64_t cells1 = 0;
-		PassResult R;
-		R.status = ST_OK, R.s = 0, R.info = 0, R.n_snap = 0, R.cells = 0;
-		if (A.step > 0 && A.want_cigar) { // low-memory first pass (reference mwf_wfa_exact, miniwfa.c:610-611)
-			const PassResult R1 = forward_pass<T, false, true>(A, M, sh, 0, false);
-			cells1 = R1.cells;
-			status = R1.status;
-			if (status == ST_OK) {
-				if (threadIdx.x == 0) sh.word[2] = trace_checkpoints(A, M, R1.n_snap, R1.info);
-				__syncthreads();
-				status = uni(sh.word[2]);
-				n_seg = R1.n_snap;
-			}
-			__syncthreads();
-		}
-		if (status == ST_OK) {
-			R = A.want_cigar ? forward_pass<T, true, false>(A, M, sh, n_seg, trace) : forward_pass<T, false, false>(A, M, sh, 0, trace);
-			status = R.status;
-		}
-		finish_pair(fresh(A), M, slot, pair, R, status, cells1);
+		align_pair<T, false, false, false, -1>(A, sh, (int32_t)blockIdx.x, pair);
 	}
 }
 
 } // namespace
 
-// Start of an align call: every pair "not run" (status -1, s -2: not final), CIGAR pool and work queue at zero.
-__global__ void reset_kernel(int32_t *status, int32_t *s, int32_t n, unsigned long long *cig_head, int32_t *queue, int32_t n_queue)
-{
-	const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-	if (i < n) status[i] = -1, s[i] = -2;
-	if (i < n_queue) queue[i] = 0; // the work counters of the align call's launches (the grid covers n_queue)
-	if (i == 0) cig_head[0] = 0ull, cig_head[1] = 0ull, cig_head[2] = 0ull, cig_head[3] = 0ull; // (the second word: flags of the align's kernels for the host, BatchArgs::cig_head + 1; the third and fourth: BatchArgs::retry_count of the two lane classes)
-}
+// ---- the built instantiations, stated once: 14 of wfa_batch_kernel and wfa_bigring_kernel<256> (tests/generic_matrix.py holds the same table and
+// compares it with the object's symbols).  Hands f the kernel, its thread count and its MODE; false: no such form is built.
+//   big                        the big-ring kernel, whatever else is asked
+//   block forms                64 ... 1024 threads, stream (four columns per lane) or scalar, MODE -1
+//   LDS2 forms (stream only)   the plan (run_batch_kernel) takes 768 threads with 32-bit rows and for traceback on 16-bit rows, 512 threads score-only on
+//                              16-bit rows: four forms
+typedef void (*GenericKernel)(const BatchArgs);
 
-int launch_reset(int32_t *status, int32_t *s, int32_t n, unsigned long long *cig_head, int32_t *queue, int32_t n_queue, void *stream)
-{
-	const int grid = (std::max(n, n_queue) + 255) / 256 > 0 ? (std::max(n, n_queue) + 255) / 256 : 1;
-	hipLaunchKernelGGL(reset_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, status, s, n, cig_head, queue, n_queue);
-	return hipGetLastError() == hipSuccess ? 0 : -2;
-}
+template <int T>
+static GenericKernel block_form(bool stream) { return stream ? &wfa_batch_kernel<T, true> : &wfa_batch_kernel<T, false>; }
 
-// ---- divergence sketch of a device-resident batch (mwf_gpu_batch_wrap: the host never sees the bytes).  The same statistic as
-// host::estimate_divergence (mwf_memory.cpp) computes while it packs a batch from host memory: how many of the 8-mers of a query's
-// prefix (up to 1500 bases) occur in its target's prefix — (1 - d)^8 plus chance hits.  One workgroup per sampled pair (at most 16:
-// pair k n / samples), the 4^8-bit set in LDS; out[k] = hits.  The reference has no size classes to get wrong (one loop serves any
-// divergence, miniwfa.c:396-426): this is what lets the classes of a WRAPPED batch follow its divergence too.
-constexpr int kSketchK = 8, kSketchLen = 1500;
-__device__ __forceinline__ uint32_t sketch_kmer(const uint8_t *p)
+template <typename F>
+static bool with_generic_form(bool big, int block, bool stream, bool lds2, bool ring16, bool want_cigar, F &&f)
 {
-	uint32_t h = 0;
-#pragma unroll
-	for (int i = 0; i < kSketchK; ++i) h = (h << 2) | ((p[i] >> 1) & 3u);
-	return h;
-}
-// hits of the query's 8-mers in the target: the calling workgroup's 256 threads, the 4^8-bit set in LDS; the count lands in *hits
-__device__ __forceinline__ void sketch_hits(const uint8_t *t, int32_t lt, const uint8_t *q, int32_t lq, uint32_t *bits, int32_t *hits)
-{
-	for (int32_t j = threadIdx.x; j < (1 << (2 * kSketchK)) / 32; j += 256) bits[j] = 0;
-	if (threadIdx.x == 0) *hits = 0;
-	__syncthreads();
-	for (int32_t j = threadIdx.x; j + kSketchK <= lt; j += 256) {
-		const uint32_t h = sketch_kmer(t + j);
-		atomicOr(&bits[h >> 5], 1u << (h & 31));
+	if (big) return f(&wfa_bigring_kernel<256>, 256, -1), true;
+	if (lds2) {
+		if (!stream) return false;
+		if (ring16 && want_cigar && block == 768) f(&wfa_batch_kernel<768, true, true, true, 1>, 768, 1);
+		else if (ring16 && !want_cigar && block == 512) f(&wfa_batch_kernel<512, true, true, true, 0>, 512, 0);
+		else if (!ring16 && want_cigar && block == 768) f(&wfa_batch_kernel<768, true, true, false, 1>, 768, 1);
+		else if (!ring16 && block == 768) f(&wfa_batch_kernel<768, true, true, false, 0>, 768, 0);
+		else return false;
+		return true;
 	}
-	__syncthreads();
-	int32_t mine = 0;
-	for (int32_t j = threadIdx.x; j + kSketchK <= lq; j += 256) {
-		const uint32_t h = sketch_kmer(q + j);
-		mine += (int32_t)((bits[h >> 5] >> (h & 31)) & 1u);
+	switch (block) {
+	case 64:   f(block_form<64>(stream), 64, -1); break;
+	case 128:  f(block_form<128>(stream), 128, -1); break;
+	case 256:  f(block_form<256>(stream), 256, -1); break;
+	case 512:  f(block_form<512>(stream), 512, -1); break;
+	case 1024: f(block_form<1024>(stream), 1024, -1); break;
+	default: return false;
 	}
-	if (mine) atomicAdd(hits, mine);
-	__syncthreads();
-}
-__global__ __launch_bounds__(256) void sketch_kernel(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql,
-                                                      int32_t n, int32_t samples, int32_t *out)
-{
-	__shared__ uint32_t bits[(1 << (2 * kSketchK)) / 32];
-	__shared__ int32_t hits;
-	const int32_t i = (int32_t)((int64_t)blockIdx.x * n / samples);
-	sketch_hits(seqs + t_off[i], min(tl[i], kSketchLen), seqs + q_off[i], min(ql[i], kSketchLen), bits, &hits);
-	if (threadIdx.x == 0) out[blockIdx.x] = hits;
-}
-
-int launch_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, int32_t n, int32_t samples, int32_t *out, void *stream)
-{
-	hipLaunchKernelGGL(sketch_kernel, dim3(samples), dim3(256), 0, (hipStream_t)stream, seqs, t_off, tl, q_off, ql, n, samples, out);
-	return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// ---- per-pair work sketch (mwf_plan.cpp: the deal order of the band classes on the shared work counter).  A pair's penalty s — and with it the
-// penalties its workgroup runs — grows with its divergence, and an equal-length batch at 5 % holds pairs of s 2118 ... 2838: dealt by length, the
-// last ones finish far apart while CUs idle.  The same statistic as sketch_kernel over the WHOLE sequences (a 1500-base prefix correlates 0.34 with s,
-// the whole pair 0.88): one workgroup per pair order[k] (order null: pair k), out[k] = hits.  ~20 kB read per 10 kb pair, once per plan.
-__global__ __launch_bounds__(256) void pair_sketch_kernel(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql,
-                                                           const int32_t *order, int32_t *out)
-{
-	__shared__ uint32_t bits[(1 << (2 * kSketchK)) / 32];
-	__shared__ int32_t hits;
-	const int32_t i = order ? order[blockIdx.x] : (int32_t)blockIdx.x;
-	sketch_hits(seqs + t_off[i], tl[i], seqs + q_off[i], ql[i], bits, &hits);
-	if (threadIdx.x == 0) out[blockIdx.x] = hits;
-}
-
-int launch_pair_sketch(const uint8_t *seqs, const int64_t *t_off, const int32_t *tl, const int64_t *q_off, const int32_t *ql, const int32_t *order, int32_t n, int32_t *out, void *stream)
-{
-	if (n <= 0) return 0;
-	hipLaunchKernelGGL(pair_sketch_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, seqs, t_off, tl, q_off, ql, order, out);
-	return hipGetLastError() == hipSuccess ? 0 : -2;
+	return true;
 }
 
 // scalar_generic (comparison / fallback) runs the one-column-per-lane kernel, low-memory mode included
 static bool wants_stream(const BatchArgs &a) { return !a.scalar_generic; }
-
-template <bool STREAM>
-static int launch_batch_as(const BatchArgs &a, int grid, int block, hipStream_t st)
-{
-	switch (block) {
-	case 64:   hipLaunchKernelGGL((wfa_batch_kernel<64, STREAM>),   dim3(grid), dim3(64),   0, st, a); break;
-	case 128:  hipLaunchKernelGGL((wfa_batch_kernel<128, STREAM>),  dim3(grid), dim3(128),  0, st, a); break;
-	case 256:  hipLaunchKernelGGL((wfa_batch_kernel<256, STREAM>),  dim3(grid), dim3(256),  0, st, a); break;
-	case 512:  hipLaunchKernelGGL((wfa_batch_kernel<512, STREAM>),  dim3(grid), dim3(512),  0, st, a); break;
-	case 1024: hipLaunchKernelGGL((wfa_batch_kernel<1024, STREAM>), dim3(grid), dim3(1024), 0, st, a); break;
-	default: return -1;
-	}
-	return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 
 // E2/F2 in LDS: one 512-thread workgroup per CU with 2 x lds_e2_cols ints of dynamic LDS
 static bool wants_lds2(const BatchArgs &a, int block) { return wants_stream(a) && a.lds_e2_cols > 0 && (block == 512 || block == 768) && a.pen.e2 == 1; }
@@ -1307,72 +1181,40 @@ static void record_launch(const BatchArgs &a, int grid, int T, bool stream_form,
 
 int launch_batch(const BatchArgs &a, int grid, int block, void *stream)
 {
-	if (a.pen.nH > kMaxRing) { // a ring deeper than the LDS window tables of every other kernel
-		if (a.pen.nH > kBigRing) return -1;
-		record_launch(a, grid, 256, false, false, false, -1, true);
-		hipLaunchKernelGGL(wfa_bigring_kernel<256>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-		return hipGetLastError() == hipSuccess ? 0 : -2;
-	}
-	if (wants_lds2(a, block)) {
-		// the plan (run_batch_kernel) takes 768 threads with 32-bit rows and for traceback on 16-bit rows, 512 threads score-only on 16-bit rows: the
-		// four forms below are the ones it can ask for
-		const int lds = a.lds_e2_cols * 2 * (a.ring16 ? 2 : 4); // E2 and F2, as 16-bit codes with the 16-bit ring rows
-		const int lds_max = a.lds_e2_cols * 2 * 4;
-		auto go = [&](auto kernel, int threads) {
-			record_launch(a, grid, threads, true, true, a.ring16 != 0, a.want_cigar ? 1 : 0, false);
+	const bool big = a.pen.nH > kMaxRing; // a ring deeper than the LDS window tables of every other kernel
+	if (big && a.pen.nH > kBigRing) return -1;
+	const bool lds2 = !big && wants_lds2(a, block), stream_form = !big && wants_stream(a), h16 = lds2 && a.ring16 != 0;
+	const int lds = lds2 ? a.lds_e2_cols * 2 * (a.ring16 ? 2 : 4) : 0; // E2 and F2, as 16-bit codes with the 16-bit ring rows
+	const int lds_max = a.lds_e2_cols * 2 * 4;
+	const bool built = with_generic_form(big, block, stream_form, lds2, h16, a.want_cigar != 0, [&](GenericKernel kernel, int threads, int mode) {
+		record_launch(a, grid, threads, stream_form, lds2, h16, mode, big);
+		if (lds2) {
 			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
 			(void)hipGetLastError();
-			hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, (hipStream_t)stream, a);
-		};
-		if (a.ring16 && a.want_cigar && block == 768) go(&wfa_batch_kernel<768, true, true, true, 1>, 768);
-		else if (a.ring16 && !a.want_cigar && block == 512) go(&wfa_batch_kernel<512, true, true, true, 0>, 512);
-		else if (!a.ring16 && a.want_cigar && block == 768) go(&wfa_batch_kernel<768, true, true, false, 1>, 768);
-		else if (!a.ring16 && block == 768) go(&wfa_batch_kernel<768, true, true, false, 0>, 768);
-		else return -1; // (no such form is built)
-		return hipGetLastError() == hipSuccess ? 0 : -2;
-	}
-	if (block != 64 && block != 128 && block != 256 && block != 512 && block != 1024) return -1;
-	record_launch(a, grid, block, wants_stream(a), false, false, -1, false);
-	return wants_stream(a) ? launch_batch_as<true>(a, grid, block, (hipStream_t)stream) : launch_batch_as<false>(a, grid, block, (hipStream_t)stream);
+		}
+		hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, (hipStream_t)stream, a);
+	});
+	if (!built) return -1;
+	return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-template <bool STREAM>
-static int occupancy_as(int block)
+static int form_occupancy(bool big, int block, bool stream, bool lds2, bool ring16, bool want_cigar, size_t lds)
 {
 	int n = 0;
 	hipError_t e = hipErrorInvalidValue;
-	switch (block) {
-	case 64:   e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<64, STREAM>, 64, 0); break;
-	case 128:  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<128, STREAM>, 128, 0); break;
-	case 256:  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<256, STREAM>, 256, 0); break;
-	case 512:  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<512, STREAM>, 512, 0); break;
-	case 1024: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<1024, STREAM>, 1024, 0); break;
-	default: break;
-	}
+	with_generic_form(big, block, stream, lds2, ring16, want_cigar, [&](GenericKernel kernel, int threads, int) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds); });
 	return e == hipSuccess ? n : 0;
 }
 
-int bigring_kernel_occupancy()
-{
-	int n = 0;
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_bigring_kernel<256>, 256, 0) == hipSuccess ? n : 0;
-}
+int bigring_kernel_occupancy() { return form_occupancy(true, 256, false, false, false, false, 0); }
 
 int batch_kernel_occupancy(int block, bool stream_pass, int lds_e2_cols, bool ring16)
 {
-	if (stream_pass && lds_e2_cols > 0 && (block == 512 || block == 768)) {
-		int n = 0;
-		const size_t lds = (size_t)lds_e2_cols * (ring16 ? 4 : 8);
-		hipError_t e;
-		// (the forms the plan launches: with 32-bit rows the traceback kernel on 768 threads — its score-only twin never holds fewer workgroups —, with 16-bit
-		// rows the traceback kernel on 768 and the score-only one on 512)
-		if (ring16) e = block == 768 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<768, true, true, true, 1>, 768, lds)
-		                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<512, true, true, true, 0>, 512, lds);
-		else if (block == 768) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wfa_batch_kernel<768, true, true, false, 1>, 768, lds);
-		else return 0;
-		return e == hipSuccess ? n : 0;
-	}
-	return stream_pass ? occupancy_as<true>(block) : occupancy_as<false>(block);
+	// the LDS2 forms the plan launches: with 32-bit rows the traceback kernel on 768 threads stands for both modes — its score-only twin never holds fewer
+	// workgroups — and 512 threads is no form (0); with 16-bit rows the traceback kernel on 768 and the score-only one on 512
+	if (stream_pass && lds_e2_cols > 0 && (block == 512 || block == 768))
+		return form_occupancy(false, block, true, true, ring16, ring16 ? block == 768 : true, (size_t)lds_e2_cols * (ring16 ? 4 : 8));
+	return form_occupancy(false, block, stream_pass, false, false, false, 0);
 }
 
 } // namespace mwf

@@ -280,8 +280,8 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 			// 32-bit: one workgroup per CU either way (128 KB of LDS): twelve waves fit its 168-VGPR budget, 490 ms against 519 ms with eight
 			// 16-bit: 512 threads, two workgroups per CU (64 KB of LDS each, 128 VGPRs) — 354 ms on 1250 x 50 kb against 375 ms for
 			// 768 threads and one per CU (479 ms with 32-bit rows); with traceback the 512-thread copy spills too much: 768 (451 against 477 ms)
-			// (mwf_kernels.hip launch_batch and batch_kernel_occupancy build exactly these three LDS2 forms per MODE — 768 on 32-bit rows, 512 score-only and
-			// 768 with traceback on 16-bit rows — and answer -1 / 0 for any other: a new choice here needs its instantiation there)
+			// (the built LDS2 forms are listed once, mwf_kernels.hip with_generic_form; launch_batch and batch_kernel_occupancy answer -1 / 0 for any other:
+			// a new choice here needs its instantiation there)
 			pl.block = ring16 ? (pl.cigar ? 768 : 512) : 768;
 		}
 		if (P.nH > kMaxRing) pl.block = 256; // the big-ring form of the generic kernel (launch_batch): one column per lane, 256 threads

@@ -19,9 +19,6 @@ constexpr int kK = 2;            // chunk slots per wave
 constexpr int kEpoch = 256;      // penalties between two band shrinks (reference miniwfa.c:429)
 constexpr int kMaxP = 16;
 
-__device__ __forceinline__ int32_t from_left(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
-
 __device__ __forceinline__ int32_t ld_ag(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_ag(int32_t *p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // hand-off payload: naturally aligned 8-byte words, write-through stores and L2-served loads (sc1) on both sides
@@ -43,24 +40,6 @@ __device__ __forceinline__ void st_box(int32_t *p, const int32_t (&v)[C])
 	if constexpr (C == 4) st2_ag((u64*)p, v[0], v[1]), st2_ag((u64*)p + 1, v[2], v[3]);
 	else if constexpr (C == 2) st2_ag((u64*)p, v[0], v[1]);
 	else st_ag(p, v[0]);
-}
-
-__device__ __forceinline__ uint32_t probe4g(const PairMem &M, int32_t j, int32_t i)
-{
-	uint32_t a, b;
-	__builtin_memcpy(&a, M.ts + j, 4);
-	__builtin_memcpy(&b, M.qs + i, 4);
-	return a ^ b;
-}
-
-__device__ __forceinline__ uint32_t inm_bit(int32_t d, int32_t k, int32_t tl, int32_t ql)
-{
-	return (uint32_t)((uint32_t)(k + 1) < (uint32_t)(tl + 1)) & (uint32_t)((uint32_t)(d + k + 1) < (uint32_t)(ql + 1));
-}
-
-__device__ __forceinline__ int32_t pick4(int32_t i, int32_t a0, int32_t a1, int32_t a2, int32_t a3)
-{
-	return i == 0 ? a0 : i == 1 ? a1 : i == 2 ? a2 : a3;
 }
 
 // C = columns per lane (4, 2 or 1): a slot computes 64 C columns.  The fewer, the fewer instructions a wave issues per penalty —
