@@ -293,6 +293,54 @@ int32_t mwf_alphabet_class16(int32_t tl, const char *ts, int32_t ql, const char 
  * before the first align and when that align ran with the tunable off. */
 int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out);
 
+/* ---- Ends-free (semi-global) alignment (kernel: csrc/mwf_ends.hip) ---- */
+
+/* Every other call here aligns both sequences end to end.  A caller behind a mapper holds a window around a seed hit, not the interval a read
+ * aligns to; an ends-free alignment leaves bases at the ends of the sequences unaligned at no cost, up to four allowances.
+ *
+ * Allowances.  Each is the largest number of bases that may be left unaligned, free of charge, at the begin or the end of the target or the query.
+ * Each must be >= 0 and is clamped to that sequence's length; one set applies to every pair of a batch.  The usual sets:
+ * read in window {INT32_MAX, INT32_MAX, 0, 0}; extension from an anchor {0, INT32_MAX, 0, INT32_MAX}; overlap {0, INT32_MAX, longest overhang, 0} and its mirror
+ * (penalties only: with t_end and q_beg — or t_beg and q_end — both unbounded the empty alignment in that corner of the matrix costs nothing and always wins).
+ *
+ * The result is the cheapest global alignment, under opt's two-piece affine penalties, of t[tb, te) against q[qb, qe) where
+ *   - at most one of tb, qb is non-zero: tb <= t_beg with qb == 0, or qb <= q_beg with tb == 0;
+ *   - te == tl or qe == ql, with tl - te <= t_end and ql - qe <= q_end.
+ *
+ * How it is found (conventions: diagonal d = i - k, query index minus target index, in column d + tl + 1; an H value k is the index of the last target
+ * base consumed, i = d + k that of the last query base):
+ *   Penalty 0.  The window is the diagonals [-min(t_beg, tl), min(q_beg, ql)]; H[d] = (d < 0 ? -d : 0) - 1, then extended along matches; E and F are dead.
+ *   End rule.  Evaluated on every in-matrix H cell after its extension, penalty 0 included: cell (d, k) ends the alignment if i == ql-1 && tl-1-k <= t_end,
+ *   or k == tl-1 && ql-1-i <= q_end.  The answer is the first penalty that has such a cell; among several the lowest diagonal (the order of the reference's
+ *   sweep).  te = k + 1, qe = i + 1.  The traceback starts there, in the state of the cell's low three traceback bits if the extension did not move it, else 0.
+ *   Band bookkeeping and n_iter are those of the global pass: growth by one column per side, clamped to [1, tl+ql+1]; the edge rule; the shrink at every
+ *   multiple of 256; n_iter += hi-lo+1 per penalty from 1 on; the max_s / max_iter stop rules.  With four zero allowances s, n_iter and the CIGAR words are
+ *   therefore those of mwf_gpu_batch_align / mwf_wfa_exact.
+ *   Traceback.  The walk leaves the matrix with either i >= 0 query bases or k >= 0 target bases still in front of it.  With L that count,
+ *   clip = min(L, begin allowance of that sequence) bases are clipped — qb or tb — and the remaining L - clip are one I (query) or D (target) run, merged with
+ *   an adjacent run of the same operation.  The CIGAR holds only = X I D words for the aligned ranges: no clip operators.
+ *
+ * Outputs.  Per pair range[4] = {tb, te, qb, qe}, half-open.  A stopped pair (max_s / max_iter) has s == -1 and all four -1; a score-only align fills te and
+ * qe and leaves tb = qb = -1.  An empty alignment is legal (n_cigar == 0, tb == te). */
+typedef struct { int32_t t_beg, t_end, q_beg, q_end; } mwf_ends_t; /* 16 bytes */
+
+/* mwf_gpu_batch_align for an ends-free alignment: validates as it does, and also returns -2 (mwf_gpu_last_error) for a negative allowance, for
+ * MWF_F_CIGAR together with opt->step > 0 (no low-memory mode) and for max(x, o1+e1, o2+e2) >= 256.  One launch of the ends-free kernel over all pairs,
+ * longest first; always on the batch's original bytes ("alpha_remap" / "alpha16" do not apply).  mwf_gpu_get_stats reports kernel_kind 3.  Results, CIGARs,
+ * mwf_gpu_batch_summarize and mwf_gpu_batch_text work as after mwf_gpu_batch_align — summaries and text of the batch's own CIGARs describe the aligned
+ * sub-ranges t[tb, te) / q[qb, qe), foreign CIGARs the full sequences —; mwf_gpu_batch_map fails after an ends-free align.  A later mwf_gpu_batch_align on
+ * the same batch behaves as if this call had never been made. */
+int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends);
+/* The ranges of the last ends-free align, copied to range[n * 4]; waits for the stream.  Fails (negative) when the batch's last align was a plain one. */
+int mwf_gpu_batch_ranges(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *range);
+/* ... and the device array they lie in (n x 4 int32; complete once the batch is finalised, e.g. by mwf_gpu_batch_results); NULL after a plain align. */
+const int32_t *mwf_gpu_batch_dev_ranges(const mwf_gpu_batch_t *b);
+
+/* The host-buffer calls, on pooled engines as mwf_wfa_batch: r as mwf_wfa_exact fills it, range[4] (one pair) / range[n * 4] may be NULL. */
+void mwf_wfa_ends(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range);
+void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n, const int32_t *tl, const char *const *ts,
+                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range);
+
 /* Timing and counters of the most recent mwf_gpu_batch_align on this engine. */
 typedef struct {
 	double  kernel_ms;     /* HIP-event time around the alignment kernels on the engine's stream */
@@ -301,7 +349,7 @@ typedef struct {
 	int32_t n_launches;    /* kernel launches issued */
 	int32_t n_retries;     /* re-runs of pairs the kernel they ran on handed back, all causes counted: window beyond the kernel's span, 16-bit offset range, a base outside A/C/G/T, traceback arena, CIGAR pool (a pair can be re-run more than once) */
 	int32_t grid, block;   /* geometry of the dominant launch */
-	int32_t kernel_kind;   /* 0: one workgroup per pair (generic); 1: one pair across the whole device; 2: one workgroup per pair (band) */
+	int32_t kernel_kind;   /* 0: one workgroup per pair (generic); 1: one pair across the whole device; 2: one workgroup per pair (band); 3: one workgroup per pair (ends-free, mwf_gpu_batch_align_ends) */
 	int64_t dev_bytes;     /* device memory the engine holds now: workspace pools + recycled batch allocations (live batches hold their own) */
 	int64_t dev_bytes_peak;/* ... and the most it held since creation or the last mwf_gpu_set(g, "trim", 0) */
 	int32_t packed;        /* band kernels: 1 = the packed 16-bit variant (mwf_band2.hip; with block 1024: its span geometry for pairs of up to ~60 kb), 32 = the one-wave-per-pair lane kernel (mwf_lane.hip), 33 = the one-workgroup-per-pair mid kernel (mwf_mid.hip); generic kernel: 16 = 16-bit ring rows */

@@ -39,6 +39,14 @@ class MwfRst(C.Structure):
     _fields_ = [("s", C.c_int32), ("n_cigar", C.c_int32), ("n_iter", C.c_int64), ("cigar", C.POINTER(C.c_uint32))]
 
 
+class MwfEnds(C.Structure):
+    """mwf_ends_t (include/miniwfa.h), 16 bytes: the bases that may stay unaligned, free of charge, at the begin / end of target and query."""
+    _fields_ = [("t_beg", C.c_int32), ("t_end", C.c_int32), ("q_beg", C.c_int32), ("q_end", C.c_int32)]
+
+
+ENDS_FREE = 0x7fffffff  # an allowance that covers any sequence
+
+
 class GpuStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("cells", C.c_int64), ("cells_pass1", C.c_int64), ("n_launches", C.c_int32),
                 ("n_retries", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("kernel_kind", C.c_int32),
@@ -80,6 +88,7 @@ ABI_SYMBOLS = (
     "mwf_gpu_batch_map", "mwf_gpu_batch_dev_map", "mwf_gpu_batch_map_fetch",
     "mwf_cigar_text", "mwf_gpu_batch_text", "mwf_gpu_batch_dev_text", "mwf_gpu_batch_text_fetch",
     "mwf_alphabet_class", "mwf_alphabet_class16", "mwf_gpu_batch_alphabet",
+    "mwf_gpu_batch_align_ends", "mwf_gpu_batch_ranges", "mwf_gpu_batch_dev_ranges", "mwf_wfa_ends", "mwf_wfa_ends_batch",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -189,6 +198,16 @@ def lib() -> C.CDLL:
     L.mwf_alphabet_class16.restype = C.c_int32
     L.mwf_gpu_batch_alphabet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mwf_gpu_batch_alphabet.restype = C.c_int
+    L.mwf_gpu_batch_align_ends.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), P(MwfEnds)]
+    L.mwf_gpu_batch_align_ends.restype = C.c_int
+    L.mwf_gpu_batch_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_ranges.restype = C.c_int
+    L.mwf_gpu_batch_dev_ranges.argtypes = [C.c_void_p]
+    L.mwf_gpu_batch_dev_ranges.restype = C.c_void_p
+    L.mwf_wfa_ends.argtypes = [C.c_void_p, P(MwfOpt), P(MwfEnds), C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, P(MwfRst), C.c_void_p]
+    L.mwf_wfa_ends.restype = None
+    L.mwf_wfa_ends_batch.argtypes = [C.c_void_p, P(MwfOpt), P(MwfEnds), C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p]
+    L.mwf_wfa_ends_batch.restype = None
     L.mwf_gpu_test_alpha_ms.argtypes = [C.c_void_p, P(C.c_double)]
     L.mwf_gpu_test_alpha_ms.restype = C.c_int
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
@@ -328,6 +347,31 @@ def wfa_batch_multi(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, devices: 
     dv = (C.c_int32 * len(devices))(*devices) if devices else None
     lib().mwf_wfa_batch_multi(km, C.byref(opt), n, tl, ts, ql, qs, r, len(devices) if devices else n_dev, dv)
     return [_take(r[i], km) for i in range(n)]
+
+
+def wfa_ends_batch(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, t_beg: int = 0, t_end: int = 0, q_beg: int = 0, q_end: int = 0, km=None):
+    """mwf_wfa_ends_batch: ends-free alignment of host buffers -> list of (s, n_iter, cigar, (tb, te, qb, qe))."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    ends = MwfEnds(t_beg, t_end, q_beg, q_end)
+    tl = (C.c_int32 * n)(*[len(t) for t, _ in pairs])
+    ql = (C.c_int32 * n)(*[len(q) for _, q in pairs])
+    ts = (C.c_char_p * n)(*[t for t, _ in pairs])
+    qs = (C.c_char_p * n)(*[q for _, q in pairs])
+    r = (MwfRst * n)()
+    rng = np.zeros((n, 4), dtype=np.int32)
+    lib().mwf_wfa_ends_batch(km, C.byref(opt), C.byref(ends), n, tl, ts, ql, qs, r, rng.ctypes.data)
+    return [_take(r[i], km) + (tuple(int(v) for v in rng[i]),) for i in range(n)]
+
+
+def wfa_ends(t: bytes, q: bytes, opt: MwfOpt, t_beg: int = 0, t_end: int = 0, q_beg: int = 0, q_end: int = 0, km=None):
+    """mwf_wfa_ends: one ends-free alignment -> (s, n_iter, cigar words or None, (tb, te, qb, qe))."""
+    ends = MwfEnds(t_beg, t_end, q_beg, q_end)
+    r = MwfRst()
+    rng = np.zeros(4, dtype=np.int32)
+    lib().mwf_wfa_ends(km, C.byref(opt), C.byref(ends), len(t), t, len(q), q, C.byref(r), rng.ctypes.data)
+    return _take(r, km) + (tuple(int(v) for v in rng),)
 
 
 def cigar2score(opt: MwfOpt, cigar: Sequence[int]):
@@ -478,6 +522,26 @@ class Batch:
         rc = lib().mwf_gpu_batch_align(self.eng.h, self.h, C.byref(opt))
         if rc != 0:
             raise RuntimeError(f"align failed ({rc}): " + self.eng.error())
+
+    def align_ends(self, opt: MwfOpt, t_beg: int = 0, t_end: int = 0, q_beg: int = 0, q_end: int = 0):
+        """Enqueue an ends-free alignment (mwf_gpu_batch_align_ends): up to t_beg / q_beg bases in front of and t_end / q_end bases behind the aligned
+        ranges are free (ENDS_FREE: any number).  results(), cigar(), summary() and texts() work as after align(); ranges() gives what was aligned."""
+        ends = MwfEnds(t_beg, t_end, q_beg, q_end)
+        rc = lib().mwf_gpu_batch_align_ends(self.eng.h, self.h, C.byref(opt), C.byref(ends))
+        if rc != 0:
+            raise RuntimeError(f"align_ends failed ({rc}): " + self.eng.error())
+
+    def ranges(self) -> np.ndarray:
+        """int32[n, 4]: (tb, te, qb, qe) of every pair of the last align_ends(), half-open; waits for the stream.  Raises after a plain align()."""
+        out = np.zeros((max(1, self.n), 4), dtype=np.int32)
+        rc = lib().mwf_gpu_batch_ranges(self.eng.h, self.h, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"ranges failed ({rc}): " + self.eng.error())
+        return out[:self.n]
+
+    def dev_ranges_ptr(self) -> int | None:
+        """Device pointer to the n x 4 int32 ranges of the last align_ends(); None after a plain align()."""
+        return lib().mwf_gpu_batch_dev_ranges(self.h)
 
     def results(self):
         """(s[int32], n_iter[int64], n_cigar[int32]) as numpy arrays; waits for the stream."""

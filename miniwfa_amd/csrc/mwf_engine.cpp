@@ -187,7 +187,7 @@ void mwf_gpu_batch_free(mwf_gpu_batch_t *b)
 	if (g->res_pin_owner == b) g->res_pin_owner = nullptr;
 	give_block(g, g->spare_block, b->block);
 	give_block(g, g->spare_cig, b->cig);
-	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1], &b->alpha_cls, &b->alpha_arena}) release(g, *d); // (hipFree waits for a kernel still writing them)
+	for (DevBuf *d : {&b->ops_summary, &b->ops_map[0], &b->ops_map[1], &b->ops_map_off[0], &b->ops_map_off[1], &b->alpha_cls, &b->alpha_arena, &b->ends_buf}) release(g, *d); // (hipFree waits for a kernel still writing them)
 	for (int k = 0; k < MWF_TXT_KINDS; ++k) release(g, b->ops_text[k]), release(g, b->ops_text_off[k]);
 	delete b;
 }
@@ -212,6 +212,19 @@ int mwf_gpu_batch_results(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *s, int64_t 
 const int32_t *mwf_gpu_batch_dev_scores(const mwf_gpu_batch_t *b) { return b ? b->d_s : nullptr; }
 const int64_t *mwf_gpu_batch_dev_iters(const mwf_gpu_batch_t *b) { return b ? b->d_iter : nullptr; }
 const int32_t *mwf_gpu_batch_dev_status(const mwf_gpu_batch_t *b) { return b ? b->d_status : nullptr; }
+
+/* the ranges {tb, te, qb, qe} of an ends-free align (mwf_gpu_batch_align_ends) */
+const int32_t *mwf_gpu_batch_dev_ranges(const mwf_gpu_batch_t *b) { return b && b->ends_last ? b->d_range : nullptr; }
+
+int mwf_gpu_batch_ranges(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *range)
+{
+	if (!g || !b || !range) return -1;
+	(void)hipSetDevice(g->device);
+	if (!b->ends_last) { g->err = "mwf_gpu_batch_ranges: the batch's last align was not ends-free (mwf_gpu_batch_align_ends)"; return -2; }
+	if (int rc = finalize(g, b)) return rc;
+	if (b->n == 0) return 0;
+	return download(g, range, b->d_range, (size_t)b->n * 16);
+}
 
 int32_t mwf_gpu_batch_cigar(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t i, uint32_t *dst, int32_t cap)
 {
@@ -257,6 +270,8 @@ static CigarOpsArgs ops_args(const mwf_gpu_batch_t *b)
 	CigarOpsArgs a{};
 	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql, a.n_pairs = b->n;
 	a.words = b->d_cig_pool, a.word_off = b->d_cigoff, a.n_words = b->d_ncig, a.status = b->d_status;
+	// after an ends-free align the batch's own CIGARs align the sub-ranges t[tb, te) / q[qb, qe): the geometry the kernel wrote beside the ranges
+	if (b->ends_last) a.t_off = b->d_sub_t_off, a.q_off = b->d_sub_q_off, a.tl = b->d_sub_tl, a.ql = b->d_sub_ql;
 	return a;
 }
 
@@ -286,7 +301,7 @@ int mwf_gpu_batch_summarize(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *o
 	if (b->n == 0) { b->summary_valid = true; return 0; }
 	if (ensure(g, b->ops_summary, (size_t)b->n * sizeof(mwf_aln_summary_t))) return -1;
 	CigarOpsArgs a = ops_args(b);
-	if (!own) a.words = d_words, a.word_off = d_word_off, a.n_words = d_n_words, a.status = nullptr;
+	if (!own) a.words = d_words, a.word_off = d_word_off, a.n_words = d_n_words, a.status = nullptr, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // (foreign CIGARs: the full sequences)
 	a.x = o.x, a.o1 = o.o1, a.e1 = o.e1, a.o2 = o.o2, a.e2 = o.e2;
 	a.mode = 0, a.summary = (int32_t*)b->ops_summary.p;
 	if (launch_cigar_ops(a, ops_block(b), g->stream)) { g->err = "kernel launch failed (CIGAR summary)"; return -1; }
@@ -311,6 +326,7 @@ int mwf_gpu_batch_map(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t which)
 {
 	if (!g || !b || which < 0 || which > 1) return -1;
 	(void)hipSetDevice(g->device);
+	if (b->ends_last) { g->err = "mwf_gpu_batch_map: the batch's last align was ends-free (coordinate maps exist for global alignments only)"; return -2; }
 	if (int rc = own_cigars(g, b, "mwf_gpu_batch_map")) return rc;
 	b->map_valid[which] = false;
 	std::vector<int64_t> &off = b->h_map_off[which];
@@ -368,6 +384,7 @@ int mwf_gpu_batch_text(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t kind, const uin
 	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql, a.n_pairs = b->n;
 	a.words = b->d_cig_pool, a.word_off = b->d_cigoff, a.n_words = b->d_ncig, a.status = b->d_status;
 	if (!own) a.words = d_words, a.word_off = d_word_off, a.n_words = d_n_words, a.status = nullptr;
+	else if (b->ends_last) a.t_off = b->d_sub_t_off, a.q_off = b->d_sub_q_off, a.tl = b->d_sub_tl, a.ql = b->d_sub_ql; // (ends-free: the aligned sub-ranges, as ops_args)
 	a.kind = kind, a.off = (int64_t*)off.p;
 	const int block = ops_block(b);
 	// sizes, offsets, and the one wait: the pool's size is only known on the device
@@ -409,6 +426,7 @@ int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out)
 {
 	if (!g || !b || !host_out) return -1;
 	if (!b->aligned) { g->err = "mwf_gpu_batch_alphabet: the batch was not aligned yet (the classes are those of its last align)"; return -2; }
+	if (b->ends_last) { g->err = "mwf_gpu_batch_alphabet: the batch's last align was ends-free (it reads the original bytes and classifies nothing)"; return -2; }
 	if (!b->alpha_known) { g->err = "mwf_gpu_batch_alphabet: the batch's last align ran with \"alpha_remap\" 0 (set it to 1 before the align)"; return -2; }
 	if (b->n > 0) memcpy(host_out, b->h_alpha.data(), (size_t)b->n);
 	return 0;
@@ -676,6 +694,41 @@ void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, i
 	if (coalesce_window_us() > 0) { exact_coalesced(km, opt, tl, ts, ql, qs, r); return; } // MWF_COALESCE_US: calls of different host threads share a launch (mwf_async.cpp)
 	const int32_t dev = default_device();
 	mwf_wfa_batch_multi(km, opt, 1, &tl, &ts, &ql, &qs, r, 1, &dev);
+}
+
+// Ends-free alignment of host buffers (include/miniwfa.h, mwf_ends_t) on a pooled engine of the default device, as run_share does a plain one
+void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n, const int32_t *tl, const char *const *ts,
+                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range)
+{
+	if (n <= 0) return;
+	mwf_gpu_t *g = acquire_engine(default_device());
+	HostResult R;
+	std::vector<int32_t> ids((size_t)n), rng((size_t)n * 4);
+	std::iota(ids.begin(), ids.end(), 0);
+	mwf_gpu_batch_t *b = batch_from_host(g, n, tl, ts, ql, qs, nullptr, 0, nullptr, nullptr);
+	const bool cigar = (opt->flag & MWF_F_CIGAR) != 0;
+	if (!b) R.err = std::string("batch upload failed: ") + mwf_gpu_last_error(g);
+	else {
+		R.s.resize((size_t)n), R.ncig.resize((size_t)n), R.iter.resize((size_t)n);
+		int rc = mwf_gpu_batch_align_ends(g, b, opt, ends);
+		rc = rc || mwf_gpu_batch_results(g, b, R.s.data(), R.iter.data(), R.ncig.data());
+		rc = rc || (cigar && fetch_cigars(g, b));
+		rc = rc || mwf_gpu_batch_ranges(g, b, rng.data());
+		if (rc) R.err = std::string("ends-free alignment failed: ") + mwf_gpu_last_error(g);
+		else if (cigar) R.cig.swap(b->h_cig), R.cigoff = b->h_cigoff;
+		mwf_gpu_batch_free(b);
+	}
+	release_engine(g);
+	if (!R.err.empty()) fatal(R.err.c_str(), nullptr);
+	mwf_opt_t quiet = *opt;
+	quiet.flag &= ~MWF_F_DEBUG; // (the traceback end state that flag prints is not kept for ends-free alignments)
+	fill_results(km, &quiet, ids, R, r);
+	if (range) memcpy(range, rng.data(), (size_t)n * 16);
+}
+
+void mwf_wfa_ends(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range)
+{
+	mwf_wfa_ends_batch(km, opt, ends, 1, &tl, &ts, &ql, &qs, r, range);
 }
 
 // mwf_wfa_chain lives in mwf_chain.cpp

@@ -20,6 +20,7 @@
 #include "miniwfa.h"
 #include "kalloc.h"
 #include "mwf_internal.h"
+#include "mwf_ends.h"
 #include "mwf_plan_classes.h"
 
 namespace mwf {
@@ -49,8 +50,8 @@ constexpr int kMaxDevices = 64;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// What distinguishes two kernel variants for the occupancy query (cached_occupancy, mwf_plan.cpp).  kind 2: the band family, 0: the generic kernel; the
-// fields of the other family stay zero.
+// What distinguishes two kernel variants for the occupancy query (cached_occupancy, mwf_plan.cpp).  kind 2: the band family, 0: the generic kernel, 3: the ends-free
+// kernel (mwf_ends.hip: its block alone); the fields of the other family stay zero.
 struct OccKey {
 	int kind = 0, block = 0;
 	// band family
@@ -158,7 +159,7 @@ struct mwf_gpu_batch_s {
 	std::vector<int32_t> h_len_order; // pair ids, longest pair first (stable): what every grouping is dealt from
 	std::vector<int8_t> h_class;    // where a pair that is handed back starts again, as a PairClass: CLS_GENERIC, one of the four band classes CLS_WIDE ... CLS_MICRO, or CLS_SPAN
 	                                // (the plan's PairPlan::fallback — a biased pair carries CLS_WIDE, a lane pair CLS_MICRO; finalize() moves it on with every re-route)
-	std::vector<int8_t> h_kind;     // kernel that ran the pair last (0 generic, 1 whole-device, 2 band)
+	std::vector<int8_t> h_kind;     // kernel that ran the pair last (0 generic, 1 whole-device, 2 band, 3 ends-free)
 	float div_est = 0;              // divergence of the batch as a k-mer sketch of a few of its pairs saw it while the batch was built from host memory (0: unknown)
 	std::vector<int8_t> h_acgt;     // from the host's look at the bytes while a batch is built from host memory: 1 both sequences are plain
 	                                // A/C/G/T, 0 not (such a pair goes to the byte-wise sequence copy at once); empty: unknown (wrapped device
@@ -232,6 +233,13 @@ struct mwf_gpu_batch_s {
 	bool text_valid[MWF_TXT_KINDS] = {false, false, false, false, false, false};
 	int64_t text_total[MWF_TXT_KINDS] = {0, 0, 0, 0, 0, 0}; // bytes of text in the pool
 	int64_t ops_max_len = -1;          // longest pair (tl + ql): what the workgroup size of those kernels is chosen by (-1: not computed yet)
+	// ends-free alignment (mwf_gpu_batch_align_ends; kernel: mwf_ends.hip).  One allocation, made by the first such align and freed with the batch:
+	// [range: n x 4 int32 | sub_t_off, sub_q_off: n int64 each | sub_tl, sub_ql: n int32 each | order: n int32, longest pair first]
+	bool ends_last = false;            // the batch's last align was ends-free: h_kind is 3 for every pair, ranges exist, maps do not
+	mwf_ends_t ends{};                 // its allowances (finalize()'s re-runs use them)
+	DevBuf ends_buf;
+	int32_t *d_range = nullptr, *d_sub_tl = nullptr, *d_sub_ql = nullptr, *d_ends_order = nullptr;
+	int64_t *d_sub_t_off = nullptr, *d_sub_q_off = nullptr;
 };
 
 

@@ -429,6 +429,88 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 	return 0;
 }
 
+// One launch of the ends-free kernel (mwf_ends.hip) over pairs d_ids[0 .. n_items) on at most `slots` workgroups, under the batch's options and allowances
+// (b->opt, b->ends).  The workspace is sized as the generic kernel's branch of run_batch_kernel sizes it: the penalty of the global problem bounds the
+// ends-free one (the global alignment is one of the alignments it chooses from).
+int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const int32_t *d_ids, int32_t n_items, int slots, const GroupInfo &G, bool timed)
+{
+	const mwf_opt_t &opt = b->opt;
+	const Penalty P = make_penalty(opt);
+	const bool cigar = (opt.flag & MWF_F_CIGAR) != 0;
+	const int64_t max_len = G.max_len, max_bound = G.max_bound;
+	const int block = std::min<int64_t>(max_len + 1, 2 * max_bound + 3) >= 8192 ? 512 : 256;
+	OccKey key;
+	key.kind = 3, key.block = block;
+	auto it = g->occ_cache.find(key);
+	const int per_cu = it != g->occ_cache.end() ? it->second : (g->occ_cache[key] = ends_kernel_occupancy(block));
+	slots = std::max(1, std::min(slots, g->n_cu * std::max(1, per_cu)));
+	const int grid = std::max(1, std::min<int>(slots, n_items));
+	const int32_t W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512), GW = W / 64 + 2;
+	const int64_t ring_slot_ints = (int64_t)(P.nH + 2 * P.n1 + 2 * P.n2) * W;
+	const size_t S = (size_t)grid;
+	if (ensure(g, g->ring, S * ring_slot_ints * 4)) return -1;
+	if (ensure(g, g->good, S * (size_t)P.nH * GW * 8)) return -1;
+	int64_t rows_slot = 0, cig_scratch_slot = 0, tb_slot_bytes = 0;
+	if (cigar) {
+		rows_slot = max_bound + 2;
+		cig_scratch_slot = max_len + 2;
+		const int64_t worst = (max_bound + 1) * (max_len + 1) + 8 * (max_bound + 2); // every penalty as wide as the whole matrix
+		int64_t per = worst;
+		if ((int64_t)g->tb.bytes < (int64_t)S * worst || g->tb_budget_mb > 0) per = std::min(per, std::max<int64_t>(tb_budget_bytes(g), (int64_t)g->tb.bytes) / (int64_t)S);
+		if (g->tb_budget_mb > 0) per = std::min(per, (g->tb_budget_mb << 20) / (int64_t)S);
+		tb_slot_bytes = std::max<int64_t>(4096, per) / 4 * 4;
+		if (ensure(g, g->tb, S * (size_t)tb_slot_bytes)) return -1;
+		if (ensure(g, g->row_off, S * (size_t)rows_slot * 8)) return -1;
+		if (ensure(g, g->row_lo, S * (size_t)rows_slot * 4)) return -1;
+		if (ensure(g, g->cig_scratch, S * (size_t)cig_scratch_slot * 4)) return -1;
+	}
+	if (getenv("MWF_DEBUG"))
+		fprintf(stderr, "[libmwf_hip] kernel kind 3: block %d, %d workgroup(s) per CU, %d slots, %d pairs; grid %d, traceback %lld B per slot\n", block, per_cu, slots, n_items, grid, (long long)tb_slot_bytes);
+
+	EndsArgs e;
+	memset(&e, 0, sizeof(e));
+	BatchArgs &a = e.b;
+	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // (always the original bytes)
+	a.order = d_ids, a.n_pairs = n_items;
+	if (g->queue_clean && g->queue_next < kQueueSlots) a.queue = (int32_t*)g->queue.p + g->queue_next++;
+	else {
+		a.queue = (int32_t*)g->queue.p;
+		HIP_TRY(g, hipMemsetAsync(g->queue.p, 0, 4, g->stream)); // (stream order: the launch that used it last is complete by then)
+	}
+	a.pen = P;
+	a.want_cigar = cigar ? 1 : 0;
+	a.max_s = opt.max_s, a.max_iter = opt.max_iter;
+	a.debug_pair = -1;
+	a.ring = (int32_t*)g->ring.p, a.ring_slot_ints = ring_slot_ints, a.W = W;
+	a.good = (unsigned long long*)g->good.p, a.GW = GW;
+	a.tb = cigar ? (uint8_t*)g->tb.p : nullptr, a.tb_slot_bytes = tb_slot_bytes;
+	a.row_off = cigar ? (int64_t*)g->row_off.p : nullptr, a.row_lo = cigar ? (int32_t*)g->row_lo.p : nullptr, a.rows_slot = rows_slot;
+	a.cig_scratch = cigar ? (uint32_t*)g->cig_scratch.p : nullptr, a.cig_scratch_slot = cig_scratch_slot;
+	a.cig_pool = b->d_cig_pool, a.cig_head = b->d_cig_head, a.cig_pool_words = b->cig_pool_words;
+	a.out_s = b->d_s, a.out_iter = b->d_iter, a.out_ncig = b->d_ncig, a.out_cigoff = b->d_cigoff;
+	a.out_status = b->d_status, a.out_cells1 = b->d_cells1;
+	e.t_beg = b->ends.t_beg, e.t_end = b->ends.t_end, e.q_beg = b->ends.q_beg, e.q_end = b->ends.q_end;
+	e.out_range = b->d_range, e.sub_t_off = b->d_sub_t_off, e.sub_q_off = b->d_sub_q_off, e.sub_tl = b->d_sub_tl, e.sub_ql = b->d_sub_ql;
+
+	if (timed) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
+	std::shared_lock<std::shared_mutex> gate(g_dev_gate[g->device % kMaxDevices]); // not while a whole-device kernel runs
+	const int lrc = launch_ends(e, grid, block, g->stream);
+	gate.unlock();
+	if (lrc != 0) {
+		g->err = "kernel launch failed (ends-free)";
+		return -1;
+	}
+	b->last_grid = std::max(b->last_grid, grid);
+	if (timed) {
+		HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
+		g->ev_pending = true;
+	}
+	g->stats.n_launches += 1;
+	g->stats.grid = std::max(g->stats.grid, grid), g->stats.block = block, g->stats.kernel_kind = 3;
+	g->stats.packed = 0, g->stats.lowmem_two_pass = 0;
+	return 0;
+}
+
 // ---- whole-device kernel ------------------------------------------------------------------------------------------------
 
 // Its workgroups wait for one another, so all of them must be resident: launches on one device are serialised process-wide
@@ -1016,6 +1098,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	if (const char *why = validate(*opt)) { g->err = why; return -2; }
 	(void)hipSetDevice(g->device);
 	b->opt = *opt;
+	b->ends_last = false;
 	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
 	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
 	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
@@ -1050,6 +1133,55 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 		}
 		if (launch_classes(g, b, *opt, R, cp, preset)) return -1;
 	}
+	b->aligned = true;
+	return 0;
+}
+
+// Ends-free alignment (include/miniwfa.h, mwf_ends_t): one launch of mwf_ends.hip's kernel over all pairs, longest first.  No size classes, no whole-device
+// route, no sequence copies; the plan cache of the plain align is left alone, so that a later mwf_gpu_batch_align finds what its last one left.
+int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends)
+{
+	if (!g || !b || !opt || !ends) return -1;
+	if (const char *why = validate(*opt)) { g->err = why; return -2; }
+	if (ends->t_beg < 0 || ends->t_end < 0 || ends->q_beg < 0 || ends->q_end < 0) { g->err = "ends-free alignment: every allowance (t_beg, t_end, q_beg, q_end) must be >= 0"; return -2; }
+	if ((opt->flag & MWF_F_CIGAR) && opt->step > 0) { g->err = "ends-free alignment has no low-memory mode: MWF_F_CIGAR needs opt.step == 0"; return -2; }
+	const Penalty P0 = make_penalty(*opt);
+	if (P0.nH > kMaxRing) { g->err = "ends-free alignment: max(x, o1+e1, o2+e2) must be < 256"; return -2; }
+	(void)hipSetDevice(g->device);
+	int64_t max_len = 0;
+	for (int32_t i = 0; i < b->n; ++i) max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+	if (max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
+	b->opt = *opt, b->ends = *ends;
+	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
+	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false);
+	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
+	b->ends_last = true;
+	g->stats = mwf_gpu_stats_t{};
+	g->stats.kernel_kind = 3;
+	if (b->n == 0) { b->aligned = b->finalized = true; return 0; }
+	const size_t N = (size_t)b->n;
+	if (!b->ends_buf.p) { // [range | sub_t_off | sub_q_off | sub_tl | sub_ql | order]
+		const size_t r_bytes = align_up(N * 16, 16), o_bytes = N * 8, l_bytes = align_up(N * 4, 16);
+		if (ensure(g, b->ends_buf, r_bytes + 2 * o_bytes + 3 * l_bytes)) return -1;
+		char *base = (char*)b->ends_buf.p;
+		b->d_range = (int32_t*)base, base += r_bytes;
+		b->d_sub_t_off = (int64_t*)base, base += o_bytes;
+		b->d_sub_q_off = (int64_t*)base, base += o_bytes;
+		b->d_sub_tl = (int32_t*)base, base += l_bytes;
+		b->d_sub_ql = (int32_t*)base, base += l_bytes;
+		b->d_ends_order = (int32_t*)base;
+		if (upload_segments(g, (char*)b->d_ends_order, std::vector<Seg>{Seg{b->h_len_order.data(), N * 4}})) { release(g, b->ends_buf); return -1; }
+	}
+	if (place_results(g, b, (opt->flag & MWF_F_CIGAR) != 0)) return -1;
+	const bool was_busy = b->busy;
+	b->busy = true;
+	bool preset = false;
+	if (reset_results(g, b, was_busy, preset)) return -1;
+	GroupInfo G;
+	G.n = b->n, G.max_len = max_len;
+	for (int32_t i = 0; i < b->n; ++i) G.max_bound = std::max(G.max_bound, penalty_bound(P0, opt->max_s, b->h_tl[i], b->h_ql[i], true));
+	if (run_ends_kernel(g, b, b->d_ends_order, b->n, 1 << 30, G, true)) return -1;
+	std::fill(b->h_kind.begin(), b->h_kind.end(), (int8_t)3);
 	b->aligned = true;
 	return 0;
 }
@@ -1140,7 +1272,7 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 	const char *fail = nullptr;
 	for (int round = 0; round < 16 && !fail; ++round) {
 		// where every unfinished pair goes next: route = kind (0 generic, 1 whole-device alone, 2 band) and, for the band kernel, the class
-		std::vector<int32_t> to_generic[2], to_generic32[2], to_band_wide[2], to_band_span[2], to_band_bytes[2], same_fewer[3][2], coop_alone;
+		std::vector<int32_t> to_generic[2], to_generic32[2], to_band_wide[2], to_band_span[2], to_band_bytes[2], same_fewer[3][2], coop_alone, ends_fewer;
 		bool grow_coop = false;
 		for (size_t i = 0; i < n; ++i) {
 			const int32_t st = b->h_status[i];
@@ -1148,7 +1280,13 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 			const int kind = b->h_kind[i], step0 = b->h_flags[i] & FLAG_STEP0;
 			static const bool dbg_route = getenv("MWF_DEBUG_REROUTE") != nullptr; // (diagnostics: why a pair is run again)
 			if (dbg_route) fprintf(stderr, "[libmwf_hip] re-route: pair %zu (tl %d ql %d) status %d kind %d class %d flags %d n_iter word %lld round %d\n", i, b->h_tl[i], b->h_ql[i], st, kind, (int)b->h_class[i], (int)b->h_flags[i], (long long)b->h_iter[i], round);
-			if (st == ST_BAND_OVERFLOW && kind == 0) {
+			if (kind == 3 && st == ST_TB_OVERFLOW) { // an ends-free pair only ever runs on its own kernel: again on fewer workgroups (= larger slots)
+				if (tb_slots == 1) fail = "traceback"; // already had the whole budget
+				ends_fewer.push_back((int32_t)i);
+			} else if (kind == 3) {
+				g->err = "pair " + std::to_string(i) + " failed on the device with status " + std::to_string(st) + " (ends-free)";
+				return -3;
+			} else if (st == ST_BAND_OVERFLOW && kind == 0) {
 				to_generic32[step0].push_back((int32_t)i); // an offset outgrew the generic kernel's 16-bit ring rows: 32-bit rows
 			} else if (st == ST_ALPHABET && kind == 2 && b->h_class[i] == CLS_SPAN) {
 				b->h_class[i] = CLS_GENERIC, to_generic[step0].push_back((int32_t)i); // (the span geometry has no byte-wise form)
@@ -1203,19 +1341,33 @@ int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 			}
 			if (fail) {
 				g->err = std::string(fail) + " of pair " + std::to_string(i) + " (tl=" + std::to_string(b->h_tl[i]) + ", ql=" + std::to_string(b->h_ql[i]) +
-				         ") do not fit in device memory" + (b->opt.step > 0 ? "" : "; set opt.step > 0 (low-memory mode)");
+				         ") do not fit in device memory" + (b->opt.step > 0 || kind == 3 ? "" : "; set opt.step > 0 (low-memory mode)");
 				return -4;
 			}
 		}
-		size_t n_redo = coop_alone.size();
+		size_t n_redo = coop_alone.size() + ends_fewer.size();
 		for (int z = 0; z < 2; ++z) n_redo += to_generic[z].size() + to_generic32[z].size() + to_band_wide[z].size() + to_band_span[z].size() + to_band_bytes[z].size() + same_fewer[0][z].size() + same_fewer[2][z].size();
 		if (n_redo == 0) break;
 		b->n_retries += (int32_t)n_redo;
 		if (grow_coop) g->coop_tb_mult *= 2;
 		for (int32_t i : coop_alone)
 			if (run_coop_pair(g, b, b->opt, i, false, false)) return -1;
-		const bool shrink = !same_fewer[0][0].empty() || !same_fewer[0][1].empty() || !same_fewer[2][0].empty() || !same_fewer[2][1].empty();
+		const bool shrink = !same_fewer[0][0].empty() || !same_fewer[0][1].empty() || !same_fewer[2][0].empty() || !same_fewer[2][1].empty() || !ends_fewer.empty();
 		if (shrink) tb_slots = std::max(1, tb_slots / 8);
+		if (!ends_fewer.empty()) { // (an ends-free batch has no other list)
+			std::stable_sort(ends_fewer.begin(), ends_fewer.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; });
+			mwf_gpu_batch_t::PlanCache::GI G;
+			for (int32_t i : ends_fewer) {
+				G.max_len = std::max<int64_t>(G.max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
+				G.max_bound = std::max(G.max_bound, penalty_bound(b->opt, b->h_tl[i], b->h_ql[i], true));
+			}
+			G.n = (int32_t)ends_fewer.size();
+			DevBuf &tmp = g->retry_ids;
+			if (ensure(g, tmp, std::max<size_t>(ends_fewer.size() * 4, 4096))) return -1;
+			if (upload_segments(g, (char*)tmp.p, std::vector<Seg>{Seg{ends_fewer.data(), ends_fewer.size() * 4}})) return -1;
+			if (run_ends_kernel(g, b, (const int32_t*)tmp.p, G.n, std::max(1, std::min<int>(tb_slots, G.n)), G, false)) return -1;
+			if (hipStreamSynchronize(g->stream) != hipSuccess) return -1;
+		}
 		auto pl_low_mem = [](const mwf_opt_t &o) { return (o.flag & MWF_F_CIGAR) && o.step > 0; };
 		const Penalty Pn = make_penalty(b->opt);
 		auto nib_pair = [&](int32_t i) { // (as the plan's: the pair's copy holds image bytes and the set has 4-bit kernels — a re-run respects the class)
