@@ -10,7 +10,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmwf_hip.so")
 SOURCES = ["mwf_band2.hip", "mwf_band2_tab.hip", "mwf_band2_nib.hip", "mwf_band2_e3.hip", "mwf_band2_e4.hip", "mwf_band2_bi.hip", "mwf_band2_bi_deep.hip", "mwf_kernels.hip", "mwf_sketch.hip", "mwf_ends.hip", "mwf_lane.hip", "mwf_mid.hip", "mwf_sys.hip", "mwf_sys_deep.hip", "mwf_cigar_ops.hip", "mwf_cigar_text.hip", "mwf_alphabet.hip", "mwf_engine.cpp", "mwf_memory.cpp", "mwf_plan.cpp", "mwf_chain.cpp", "mwf_async.cpp", "kalloc.cpp", "mwf_dbg.cpp"]
-HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_ends.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_band2_kernel.h"), os.path.join(CSRC, "mwf_band2_dispatch.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(CSRC, "mwf_plan_classes.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
+HEADERS = [os.path.join(CSRC, "mwf_internal.h"), os.path.join(CSRC, "mwf_device.h"), os.path.join(CSRC, "mwf_ends.h"), os.path.join(CSRC, "mwf_sys_pass.h"), os.path.join(CSRC, "mwf_band2_kernel.h"), os.path.join(CSRC, "mwf_band2_dispatch.h"), os.path.join(CSRC, "mwf_engine.h"), os.path.join(CSRC, "mwf_plan_classes.h"), os.path.join(CSRC, "mwf_plan_retry.h"), os.path.join(ROOT, "include", "miniwfa.h"), os.path.join(ROOT, "include", "kalloc.h")]
 # the seven units of the packed band kernel (its template: mwf_band2_kernel.h, which instantiations each holds: mwf_band2_dispatch.h); `python -m miniwfa_amd.build --list-band-units`
 # prints them for the scripts under profiles/ that build a variant of them
 BAND2_UNITS = [s for s in SOURCES if s.startswith("mwf_band2")]

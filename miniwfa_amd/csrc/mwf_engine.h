@@ -158,7 +158,7 @@ struct mwf_gpu_batch_s {
 	std::vector<int32_t> h_order;   // what d_order holds: pair ids, grouped by size class, longest first inside a class
 	std::vector<int32_t> h_len_order; // pair ids, longest pair first (stable): what every grouping is dealt from
 	std::vector<int8_t> h_class;    // where a pair that is handed back starts again, as a PairClass: CLS_GENERIC, one of the four band classes CLS_WIDE ... CLS_MICRO, or CLS_SPAN
-	                                // (the plan's PairPlan::fallback — a biased pair carries CLS_WIDE, a lane pair CLS_MICRO; finalize() moves it on with every re-route)
+	                                // (the plan's PairPlan::fallback — a biased pair carries CLS_WIDE, a lane pair CLS_MICRO; every re-route moves it on: reroute_pair, mwf_plan_retry.h)
 	std::vector<int8_t> h_kind;     // kernel that ran the pair last (0 generic, 1 whole-device, 2 band, 3 ends-free)
 	float div_est = 0;              // divergence of the batch as a k-mer sketch of a few of its pairs saw it while the batch was built from host memory (0: unknown)
 	std::vector<int8_t> h_acgt;     // from the host's look at the bytes while a batch is built from host memory: 1 both sequences are plain
@@ -211,7 +211,21 @@ struct mwf_gpu_batch_s {
 		// four slots, and the kernel reports whether three would have held every pair; 1: three hold this batch under these options; 2: four are needed.
 		int8_t wide_state = 0;
 		bool wide_measured = false; // this align's first launch of the class ran on four slots with the report word zeroed
-		struct GI { int32_t n = 0; int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; } gi[kNumClasses];
+		// the maxima over a set of pairs (a class's group, the list of a re-run): what a launch sizes its kernel and workspace by
+		struct GI {
+			int32_t n = 0;
+			int64_t max_len = 0, max_bound = 0, max_bound1 = 0, max_tl = 0, max_seq_lds = 0, max_exp_win = 0; // max_seq_lds: LDS bytes that hold the longest pair's sequences as bytes
+			// one more pair: its lengths, its penalty bound with and without max_s, the window it is expected to reach
+			// (the last three by reference, as group_maxima's loop has always read them: given values the compiler pairs max_bound and max_bound1 into one 128-bit
+			// update whose 64-bit compares it has to emulate, and the first align of a 40 000-pair batch takes 0.1 ms longer; profiles/retry_refactor/plan_timing.txt)
+			void add(int64_t tl, int64_t ql, const int64_t &bound, const int64_t &bound1, const int64_t &exp_win)
+			{
+				++n;
+				max_len = std::max(max_len, tl + ql), max_bound = std::max(max_bound, bound), max_bound1 = std::max(max_bound1, bound1);
+				max_tl = std::max(max_tl, tl), max_exp_win = std::max(max_exp_win, exp_win);
+				max_seq_lds = std::max<int64_t>(max_seq_lds, ((tl + 3) & ~3LL) + 8 + ((ql + 3) & ~3LL) + 16);
+			}
+		} gi[kNumClasses];
 		std::vector<int8_t> cls0, flags0;
 	} plan;
 	std::vector<char> host_out;     // the fixed-size results as they came back (finalize)

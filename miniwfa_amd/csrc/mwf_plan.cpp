@@ -1,8 +1,9 @@
 // mwf_plan.cpp — the plan / launch / retry layer of libmwf_hip.so's host side: penalties, which kernel and geometry serves a set of pairs
-// (choose_kernel), the size classes of a batch (mwf_gpu_batch_align), one launch of the one-workgroup-per-pair kernels (run_batch_kernel), the
-// passes of the whole-device kernel (run_coop_group) and the re-runs of what did not fit where it ran (finalize).  Split from mwf_engine.cpp in
-// round 5 (no behaviour change).
+// (choose_kernel), the size classes of a batch (mwf_gpu_batch_align; the classes and their rule: mwf_plan_classes.h), one launch of the one-workgroup-per-pair
+// kernels (run_batch_kernel) or of the ends-free kernel (run_ends_kernel), the passes of the whole-device kernel (run_coop_group) and the re-runs of what did not
+// fit where it ran (finalize; the routes and their rule: mwf_plan_retry.h).  Split from mwf_engine.cpp in round 5 (no behaviour change).
 #include "mwf_engine.h"
+#include "mwf_plan_retry.h"
 
 namespace mwf {
 namespace host {
@@ -33,17 +34,28 @@ int64_t penalty_bound(const mwf_opt_t &o, int64_t tl, int64_t ql, bool honour_ma
 
 inline int64_t band_span_window() { return band_window(band2_span_chunks()); }
 
+// the per-slot workspace of a launch (size_slots)
+struct SlotSizes {
+	int32_t W = 0, GW = 0; // row stride (columns), good-bit words per row
+	int64_t ring_slot_ints = 0, rows_slot = 0, cig_scratch_slot = 0, tb_slot_bytes = 0;
+};
+
 struct Plan {
-	int kind = 0;              // 0: generic kernel, 2: band kernel
+	int kind = 0;              // 0: generic kernel, 2: band kernel, 3: ends-free kernel
 	BandGeom band{0, 0, 0, 0, 0, 0};
 	int block = 256, grid = 1;
-	int32_t W = 0, GW = 0;
-	int64_t ring_slot_ints = 0, rows_slot = 0, tb_slot_bytes = 0, cig_scratch_slot = 0;
+	SlotSizes ws;
 	int64_t snap_slot_ints = 0, snap_meta_slot = 0, seg_slot = 0;
 	bool low_mem = false, cigar = false;
 };
 
 typedef mwf_gpu_batch_t::PlanCache::GI GroupInfo;
+
+// order of pair ids: longest pair first (with std::stable_sort)
+static auto longer_first(const mwf_gpu_batch_t *b)
+{
+	return [b](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; };
+}
 
 // One launch of the one-workgroup-per-pair kernels, as its caller asks for it (run_batch_kernel).
 struct LaunchReq {
@@ -208,13 +220,15 @@ void choose_kernel(mwf_gpu_t *g, const LaunchReq &rq, const Penalty &P, Plan &pl
 int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16)
 {
 	OccKey key;
-	if (pl.kind == 2) {
+	if (pl.kind == 3) key.kind = 3, key.block = pl.block;
+	else if (pl.kind == 2) {
 		key.kind = 2, key.block = pl.band.block, key.packed = pl.band.packed, key.lane = pl.band.lane, key.slots512 = pl.band.block == 512 ? pl.band.span / 2048 : 0;
 		key.e1 = P.e1, key.e2 = P.e2, key.lds_bytes = pl.band.lds_bytes, key.cigar = pl.cigar, key.seq2 = pl.band.seq2 != 0, key.tab = pl.band.tab > 0, key.nib = pl.band.nib != 0;
 	} else key.block = pl.block, key.stream_pass = stream_pass, key.ring16 = ring16, key.big_ring = P.nH > kMaxRing, key.lds_e2_cols = lds_e2_cols;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;
-	const int per = pl.kind == 2 && pl.band.lane == 2 ? 1 // (mwf_mid.hip: most of a CU's LDS per workgroup)
+	const int per = pl.kind == 3 ? ends_kernel_occupancy(pl.block)
+	              : pl.kind == 2 && pl.band.lane == 2 ? 1 // (mwf_mid.hip: most of a CU's LDS per workgroup)
 	              : pl.kind == 2 && pl.band.lane ? lane_kernel_occupancy(pl.band.lds_bytes, pl.cigar)
 	              : pl.kind == 2 ? band2_kernel_occupancy(P, pl.band, pl.cigar)
 	              : P.nH > kMaxRing ? bigring_kernel_occupancy()
@@ -239,8 +253,82 @@ int64_t tb_budget_bytes(mwf_gpu_t *g)
 // no other kernel of this process holds CUs while its workgroups wait for one another.
 std::shared_mutex g_dev_gate[kMaxDevices];
 
+// ---- what the launch functions share ------------------------------------------------------------------------------------
+
+// generic and ends-free kernel: four waves per pair, eight once the windows are wide (measured on 1250 x 50 kb: 708 ms against 782 ms)
+static int window_block(const GroupInfo &G) { return std::min<int64_t>(G.max_len + 1, 2 * G.max_bound + 3) >= 8192 ? 512 : 256; }
+// row stride: whole 256-column chunks plus room for the band kernel's neighbour loads past the last chunk; a good-bit word per 64 columns
+static void set_row_stride(SlotSizes &ws, int64_t max_len) { ws.W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512), ws.GW = ws.W / 64 + 2; }
+// traceback bytes of a pair at worst: every penalty as wide as the whole matrix
+static int64_t tb_worst(const GroupInfo &G) { return (G.max_bound + 1) * (G.max_len + 1) + 8 * (G.max_bound + 2); }
+
+// The workspace of `grid` slots of a one-workgroup-per-pair launch, sized and allocated: rings, good bits and, in CIGAR mode, traceback arena (a slot holds `worst`
+// bytes, or its share of the budget), row metadata and CIGAR scratch.  The traceback budget is looked up here, and only when the arena has to grow.
+static int size_slots(mwf_gpu_t *g, const Penalty &P, const GroupInfo &G, int grid, bool cigar, int64_t worst, bool rings_in_lds, SlotSizes &ws)
+{
+	set_row_stride(ws, G.max_len);
+	ws.ring_slot_ints = rings_in_lds ? 64 : (int64_t)(P.nH + 2 * P.n1 + 2 * P.n2) * ws.W;
+	const size_t S = (size_t)grid;
+	if (ensure(g, g->ring, S * ws.ring_slot_ints * 4)) return -1;
+	if (ensure(g, g->good, S * (size_t)P.nH * ws.GW * 8)) return -1;
+	if (!cigar) return 0;
+	ws.rows_slot = G.max_bound + 2, ws.cig_scratch_slot = G.max_len + 2;
+	// the device is only asked how much is free when the arena at hand cannot hold the worst case
+	int64_t per = worst;
+	if ((int64_t)g->tb.bytes < (int64_t)S * worst || g->tb_budget_mb > 0) per = std::min(per, std::max<int64_t>(tb_budget_bytes(g), (int64_t)g->tb.bytes) / (int64_t)S);
+	if (g->tb_budget_mb > 0) per = std::min(per, (g->tb_budget_mb << 20) / (int64_t)S);
+	ws.tb_slot_bytes = std::max<int64_t>(4096, per) / 4 * 4; // rows are padded to dwords
+	if (ensure(g, g->tb, S * (size_t)ws.tb_slot_bytes)) return -1;
+	if (ensure(g, g->row_off, S * (size_t)ws.rows_slot * 8)) return -1;
+	if (ensure(g, g->row_lo, S * (size_t)ws.rows_slot * 4)) return -1;
+	return ensure(g, g->cig_scratch, S * (size_t)ws.cig_scratch_slot * 4);
+}
+
+// What every launch sets the same way: inputs (remapped: "alpha_remap", class-1 pairs' offsets lead to their copies), penalties and limits, the per-slot arrays and
+// their sizes, CIGAR pool, outputs.
+static void fill_args(BatchArgs &a, const mwf_gpu_t *g, const mwf_gpu_batch_t *b, const mwf_opt_t &opt, const Penalty &P, bool cigar, const SlotSizes &ws, bool remapped)
+{
+	a.seqs = b->d_seqs, a.t_off = remapped ? b->d_rt_off : b->d_t_off, a.q_off = remapped ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql;
+	a.pen = P, a.want_cigar = cigar ? 1 : 0, a.max_s = opt.max_s, a.max_iter = opt.max_iter;
+	a.debug_pair = b->debug_pair;
+	a.ring = (int32_t*)g->ring.p, a.ring_slot_ints = ws.ring_slot_ints, a.W = ws.W, a.good = (unsigned long long*)g->good.p, a.GW = ws.GW;
+	a.tb = cigar ? (uint8_t*)g->tb.p : nullptr, a.tb_slot_bytes = ws.tb_slot_bytes;
+	a.row_off = cigar ? (int64_t*)g->row_off.p : nullptr, a.row_lo = cigar ? (int32_t*)g->row_lo.p : nullptr, a.rows_slot = ws.rows_slot;
+	a.cig_scratch = cigar ? (uint32_t*)g->cig_scratch.p : nullptr, a.cig_scratch_slot = ws.cig_scratch_slot;
+	a.cig_pool = b->d_cig_pool, a.cig_head = b->d_cig_head, a.cig_pool_words = b->cig_pool_words;
+	a.out_s = b->d_s, a.out_iter = b->d_iter, a.out_ncig = b->d_ncig, a.out_cigoff = b->d_cigoff;
+	a.out_status = b->d_status, a.out_cells1 = b->d_cells1, a.out_dbg = b->d_dbg4;
+}
+
+// A fresh work counter: the first kQueueSlots launches of an align call use the ones its reset kernel zeroed, the others zero the first.
+static int take_counter(mwf_gpu_t *g, int32_t *&queue)
+{
+	if (g->queue_clean && g->queue_next < kQueueSlots) { queue = (int32_t*)g->queue.p + g->queue_next++; return 0; }
+	queue = (int32_t*)g->queue.p;
+	HIP_TRY(g, hipMemsetAsync(g->queue.p, 0, 4, g->stream)); // (stream order: the launch that used it last is complete by then)
+	return 0;
+}
+
+// The launch itself, not while a whole-device kernel runs; the events that bracket the kernels of an align call (every workspace allocation is already done); the
+// batch's largest grid and the engine's record of its last launch.
+template <class Launch>
+static int launch_gated(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, const Plan &pl, int packed, const char *what, Launch launch)
+{
+	if (rq.timed_begin) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
+	std::shared_lock<std::shared_mutex> gate(g_dev_gate[g->device % kMaxDevices]);
+	const int lrc = launch();
+	gate.unlock();
+	if (lrc != 0) { g->err = what; return -1; }
+	b->last_grid = std::max(b->last_grid, pl.grid);
+	if (rq.timed_end) HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
+	g->ev_pending |= rq.timed_end;
+	g->stats.n_launches += 1;
+	g->stats.grid = std::max(g->stats.grid, pl.grid), g->stats.block = pl.block, g->stats.kernel_kind = pl.kind;
+	g->stats.packed = packed, g->stats.lowmem_two_pass = pl.low_mem ? 1 : 0;
+	return 0;
+}
+
 // Run the one-workgroup-per-pair kernel over the request's pairs on at most rq.slots workgroups; *ran_kind: the kernel that took them (0 generic, 2 band).
-// The traceback budget is looked up here, and only when the arena has to grow.
 int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *ran_kind)
 {
 	const mwf_opt_t &opt = rq.opt;
@@ -251,8 +339,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 	Plan pl;
 	pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
 	pl.low_mem = pl.cigar && opt.step > 0;
-	// generic kernel: four waves per pair, eight once the windows are wide (measured on 1250 x 50 kb: 708 ms against 782 ms)
-	pl.block = g->block > 0 && g->block != 768 ? g->block : (std::min<int64_t>(max_len + 1, 2 * max_bound + 3) >= 8192 ? 512 : 256);
+	pl.block = g->block > 0 && g->block != 768 ? g->block : window_block(rq.group);
 	choose_kernel(g, rq, P, pl);
 	// `slots` is an upper bound from the caller (retries ask for fewer, larger slots); the chosen kernel's own residency
 	// bounds it as well
@@ -298,37 +385,14 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 	if (getenv("MWF_DEBUG"))
 		fprintf(stderr, "[libmwf_hip] kernel kind %d: block %d packed %d lds %d B, %d workgroup(s) per CU, %d slots, %d pairs; span %d seq2 %d lane %d tab %d nib %d grid %d hint %lld\n", pl.kind, pl.block,
 		        pl.band.packed, pl.band.lds_bytes, per_cu, slots, n_items, pl.band.span, pl.band.seq2, pl.band.lane, pl.band.tab, pl.band.nib, pl.grid, (long long)rq.window_hint);
-	// row stride: whole 256-column chunks plus room for the band kernel's neighbour loads past the last chunk
-	pl.W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512);
-	pl.GW = pl.W / 64 + 2;
-	pl.ring_slot_ints = (int64_t)(P.nH + 2 * P.n1 + 2 * P.n2) * pl.W;
-	if (pl.kind == 2 && pl.band.lane) pl.ring_slot_ints = 64; // its rings are in LDS
+	int64_t worst = tb_worst(rq.group);
+	// the second pass of the low-memory mode collapses the band to one diagonal at every checkpoint (miniwfa.c:413-416) and consecutive
+	// checkpoints are at most step+nH penalties apart, so a row is never wider than about 2*(step+nH)
+	if (pl.low_mem && opt.step > 2 * P.nH) worst = std::min(worst, (max_bound + 1) * std::min<int64_t>(max_len + 1, 2 * (int64_t)(opt.step + 2 * P.nH) + 8) + 8 * (max_bound + 2));
+	if (pl.kind == 2 && pl.band.lane == 1) worst = (std::min<int64_t>(max_bound, 256) + 2) * pl.band.span; // its rows: the span wide, fewer than 256 of them
+	if (pl.kind == 2 && pl.band.lane == 2) worst = (max_bound + 2) * pl.band.span;                          // rows of the span's width, one per penalty
+	if (size_slots(g, P, rq.group, pl.grid, pl.cigar, worst, pl.kind == 2 && pl.band.lane, pl.ws)) return -1; // (the lane and mid kernels' rings are in LDS)
 	const size_t S = (size_t)pl.grid;
-
-	if (ensure(g, g->ring, S * pl.ring_slot_ints * 4)) return -1;
-	if (ensure(g, g->good, S * (size_t)P.nH * pl.GW * 8)) return -1;
-	if (pl.cigar) {
-		pl.rows_slot = max_bound + 2;
-		pl.cig_scratch_slot = max_len + 2;
-		int64_t worst = (max_bound + 1) * (max_len + 1); // every penalty as wide as the whole matrix
-		if (pl.low_mem && opt.step > 2 * P.nH) {
-			// the second pass collapses the band to one diagonal at every checkpoint (miniwfa.c:413-416) and consecutive
-			// checkpoints are at most step+nH penalties apart, so a row is never wider than about 2*(step+nH)
-			worst = std::min(worst, (max_bound + 1) * std::min<int64_t>(max_len + 1, 2 * (int64_t)(opt.step + 2 * P.nH) + 8));
-		}
-		worst += 8 * (max_bound + 2);
-		if (pl.kind == 2 && pl.band.lane == 1) worst = (std::min<int64_t>(max_bound, 256) + 2) * pl.band.span; // its rows: the span wide, fewer than 256 of them
-		if (pl.kind == 2 && pl.band.lane == 2) worst = (max_bound + 2) * pl.band.span;                          // rows of the span's width, one per penalty
-		// the device is only asked how much is free when the arena at hand cannot hold the worst case
-		int64_t per = worst;
-		if ((int64_t)g->tb.bytes < (int64_t)S * worst || g->tb_budget_mb > 0) per = std::min(per, std::max<int64_t>(tb_budget_bytes(g), (int64_t)g->tb.bytes) / (int64_t)S);
-		if (g->tb_budget_mb > 0) per = std::min(per, (g->tb_budget_mb << 20) / (int64_t)S);
-		pl.tb_slot_bytes = std::max<int64_t>(4096, per) / 4 * 4; // rows are padded to dwords
-		if (ensure(g, g->tb, S * (size_t)pl.tb_slot_bytes)) return -1;
-		if (ensure(g, g->row_off, S * (size_t)pl.rows_slot * 8)) return -1;
-		if (ensure(g, g->row_lo, S * (size_t)pl.rows_slot * 4)) return -1;
-		if (ensure(g, g->cig_scratch, S * (size_t)pl.cig_scratch_slot * 4)) return -1;
-	}
 	if (pl.low_mem) {
 		const int64_t NS = P.nH + 2 * P.n1 + 2 * P.n2;
 		const int64_t n_snap_max = max_bound1 / opt.step + 2; // first pass: bound without max_s
@@ -340,7 +404,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 			worst += NS * std::min<int64_t>(max_len + 1, 2 * j * opt.step + 3);
 		const int64_t budget = (int64_t)(std::max<int64_t>(tb_budget_bytes(g), (int64_t)g->snap.bytes) / 4 / (int64_t)S);
 		pl.snap_slot_ints = std::max<int64_t>(1024, std::min(worst, budget));
-		if (ensure(g, g->sring, S * pl.ring_slot_ints * 4)) return -1;
+		if (ensure(g, g->sring, S * pl.ws.ring_slot_ints * 4)) return -1;
 		if (ensure(g, g->snap, S * (size_t)pl.snap_slot_ints * 4)) return -1;
 		if (ensure(g, g->snap_meta, S * (size_t)pl.snap_meta_slot * 4)) return -1;
 		if (ensure(g, g->seg, S * (size_t)pl.seg_slot * 8)) return -1;
@@ -348,12 +412,11 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
-	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
+	fill_args(a, g, b, opt, P, pl.cigar, pl.ws, b->alpha_active);
 	a.order = rq.d_order, a.n_pairs = n_items;
 	a.timeline = g->timeline;
 	// A launch of one workgroup per pair on the kernels that take it (lane, mid, packed band) needs no work counter: workgroup i aligns
-	// pair i.  Otherwise a fresh counter: the first kQueueSlots launches of an align call use the ones its reset kernel zeroed.
-	// The lane kernel takes a set of 64 counters (kLaneCounters above).
+	// pair i.  Otherwise a fresh counter (take_counter).  The lane kernel takes a set of 64 counters (kLaneCounters above).
 	if (pl.kind == 2 && pl.band.lane == 1 && n_items > pl.grid) {
 		a.queue_parts = kLaneCounters;
 		if (g->queue_clean && g->lane_set_next < kLaneSets) a.queue = (int32_t*)g->queue.p + kQueueSlots + (g->lane_set_next++) * kLaneCounters * kLaneStride;
@@ -363,11 +426,7 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 		}
 	} else if (pl.kind == 2 && pl.band.lane == 1) a.queue = nullptr;
 	else if (pl.kind == 2 && (pl.band.lane || pl.band.packed) && n_items <= pl.grid && !g->queue_clean) a.queue = nullptr;
-	else if (g->queue_clean && g->queue_next < kQueueSlots) a.queue = (int32_t*)g->queue.p + g->queue_next++;
-	else {
-		a.queue = (int32_t*)g->queue.p;
-		HIP_TRY(g, hipMemsetAsync(g->queue.p, 0, 4, g->stream)); // (stream order: the launch that used it last is complete by then)
-	}
+	else if (take_counter(g, a.queue)) return -1;
 	// re-runs without the host (BatchArgs::retry_ids): this launch fills the batch's list / takes its pairs from it
 	if (rq.retry_list == 1) a.retry_ids = b->d_retry_ids + rq.retry_slot * kRetryCap, a.retry_cap = kRetryCap, a.retry_count = (unsigned int*)(b->d_cig_head + 2 + rq.retry_slot);
 	if (rq.retry_list == 2) a.n_pairs_dev = (const unsigned int*)(b->d_cig_head + 2 + rq.retry_slot), a.queue = nullptr, a.queue_parts = 0;
@@ -376,21 +435,8 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 	a.lds_e2_cols = lds_e2_cols;
 	a.ring16 = ring16 ? 1 : 0;
 	a.lane_chunks = pl.kind == 2 && pl.band.lane ? pl.band.span / 64 : 0;
-	a.pen = P;
-	a.want_cigar = pl.cigar ? 1 : 0;
 	a.step = pl.low_mem ? opt.step : 0;
-	a.max_s = opt.max_s, a.max_iter = opt.max_iter;
-	a.debug_pair = b->debug_pair;
-	a.ring = (int32_t*)g->ring.p;
 	a.sring = pl.low_mem ? (int32_t*)g->sring.p : nullptr;
-	a.ring_slot_ints = pl.ring_slot_ints, a.W = pl.W;
-	a.good = (unsigned long long*)g->good.p, a.GW = pl.GW;
-	a.tb = pl.cigar ? (uint8_t*)g->tb.p : nullptr, a.tb_slot_bytes = pl.tb_slot_bytes;
-	a.row_off = pl.cigar ? (int64_t*)g->row_off.p : nullptr;
-	a.row_lo = pl.cigar ? (int32_t*)g->row_lo.p : nullptr;
-	a.rows_slot = pl.rows_slot;
-	a.cig_scratch = pl.cigar ? (uint32_t*)g->cig_scratch.p : nullptr, a.cig_scratch_slot = pl.cig_scratch_slot;
-	a.cig_pool = b->d_cig_pool, a.cig_head = b->d_cig_head, a.cig_pool_words = b->cig_pool_words;
 	// block mode leaves up to one partly used block per workgroup behind; the pool's slack (batch_common) covers kCigBlockGrid of them per align —
 	// one align can make several block-mode launches (size classes, byte-wise twins, re-runs): a launch the slack no longer covers takes words singly
 	a.cig_block = 0;
@@ -399,116 +445,46 @@ int run_batch_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int 
 	a.snap = pl.low_mem ? (int32_t*)g->snap.p : nullptr, a.snap_slot_ints = pl.snap_slot_ints;
 	a.snap_meta = pl.low_mem ? (int32_t*)g->snap_meta.p : nullptr, a.snap_meta_slot = pl.snap_meta_slot;
 	a.seg = pl.low_mem ? (int32_t*)g->seg.p : nullptr, a.seg_slot = pl.seg_slot;
-	a.out_s = b->d_s, a.out_iter = b->d_iter, a.out_ncig = b->d_ncig, a.out_cigoff = b->d_cigoff;
-	a.out_status = b->d_status, a.out_cells1 = b->d_cells1, a.out_dbg = b->d_dbg4;
 	a.dbg = b->debug_pair >= 0 ? (int32_t*)g->dbg.p : nullptr;
 	a.dbg_cap = b->debug_pair >= 0 ? (int32_t)(g->dbg.bytes / 8) : 0;
 
-	// HIP events bracket the kernel only: every workspace allocation above is already done
-	if (rq.timed_begin) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
-	std::shared_lock<std::shared_mutex> gate(g_dev_gate[g->device % kMaxDevices]); // not while a whole-device kernel runs
-	const int lrc = pl.kind == 2 && pl.band.lane == 2 ? launch_mid(a, pl.grid, pl.band.block, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
-	              : pl.kind == 2 && pl.band.lane ? launch_lane(a, pl.grid, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
-	              : pl.kind == 2 ? launch_band2(a, pl.grid, pl.band, g->stream)
-	                             : launch_batch(a, pl.grid, pl.block, g->stream);
-	gate.unlock();
-	if (lrc != 0) {
-		g->err = "kernel launch failed";
-		return -1;
-	}
-	b->last_grid = std::max(b->last_grid, pl.grid);
-	if (rq.timed_end) { // the events bracket all launches of an align call, not the retries
-		HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
-		g->ev_pending = true;
-	}
-	g->stats.n_launches += 1;
-	g->stats.grid = std::max(g->stats.grid, pl.grid), g->stats.block = pl.block, g->stats.kernel_kind = pl.kind;
-	g->stats.packed = pl.kind == 2 ? (pl.band.lane == 2 ? 33 : pl.band.lane ? 32 : (pl.band.packed ? 1 : 0)) : (ring16 ? 16 : 0);
-	g->stats.lowmem_two_pass = pl.low_mem ? 1 : 0;
+	const int packed = pl.kind == 2 ? (pl.band.lane == 2 ? 33 : pl.band.lane ? 32 : (pl.band.packed ? 1 : 0)) : (ring16 ? 16 : 0);
 	if (ran_kind) *ran_kind = pl.kind;
-	return 0;
+	return launch_gated(g, b, rq, pl, packed, "kernel launch failed", [&] {
+		return pl.kind == 2 && pl.band.lane == 2 ? launch_mid(a, pl.grid, pl.band.block, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
+		     : pl.kind == 2 && pl.band.lane ? launch_lane(a, pl.grid, pl.band.lds_bytes, pl.band.seq2 != 0, g->stream)
+		     : pl.kind == 2 ? launch_band2(a, pl.grid, pl.band, g->stream)
+		                    : launch_batch(a, pl.grid, pl.block, g->stream);
+	});
 }
 
-// One launch of the ends-free kernel (mwf_ends.hip) over pairs d_ids[0 .. n_items) on at most `slots` workgroups, under the batch's options and allowances
-// (b->opt, b->ends).  The workspace is sized as the generic kernel's branch of run_batch_kernel sizes it: the penalty of the global problem bounds the
-// ends-free one (the global alignment is one of the alignments it chooses from).
-int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const int32_t *d_ids, int32_t n_items, int slots, const GroupInfo &G, bool timed)
+// One launch of the ends-free kernel (mwf_ends.hip) over the request's pairs on at most rq.slots workgroups, under the batch's allowances (b->ends); of the request it
+// reads the options, the pairs, the slots, the maxima and the events.  The workspace is the generic kernel's: the penalty of the global problem bounds the ends-free
+// one (the global alignment is one of the alignments it chooses from).
+int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *ran_kind)
 {
-	const mwf_opt_t &opt = b->opt;
+	const mwf_opt_t &opt = rq.opt;
 	const Penalty P = make_penalty(opt);
-	const bool cigar = (opt.flag & MWF_F_CIGAR) != 0;
-	const int64_t max_len = G.max_len, max_bound = G.max_bound;
-	const int block = std::min<int64_t>(max_len + 1, 2 * max_bound + 3) >= 8192 ? 512 : 256;
-	OccKey key;
-	key.kind = 3, key.block = block;
-	auto it = g->occ_cache.find(key);
-	const int per_cu = it != g->occ_cache.end() ? it->second : (g->occ_cache[key] = ends_kernel_occupancy(block));
-	slots = std::max(1, std::min(slots, g->n_cu * std::max(1, per_cu)));
-	const int grid = std::max(1, std::min<int>(slots, n_items));
-	const int32_t W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512), GW = W / 64 + 2;
-	const int64_t ring_slot_ints = (int64_t)(P.nH + 2 * P.n1 + 2 * P.n2) * W;
-	const size_t S = (size_t)grid;
-	if (ensure(g, g->ring, S * ring_slot_ints * 4)) return -1;
-	if (ensure(g, g->good, S * (size_t)P.nH * GW * 8)) return -1;
-	int64_t rows_slot = 0, cig_scratch_slot = 0, tb_slot_bytes = 0;
-	if (cigar) {
-		rows_slot = max_bound + 2;
-		cig_scratch_slot = max_len + 2;
-		const int64_t worst = (max_bound + 1) * (max_len + 1) + 8 * (max_bound + 2); // every penalty as wide as the whole matrix
-		int64_t per = worst;
-		if ((int64_t)g->tb.bytes < (int64_t)S * worst || g->tb_budget_mb > 0) per = std::min(per, std::max<int64_t>(tb_budget_bytes(g), (int64_t)g->tb.bytes) / (int64_t)S);
-		if (g->tb_budget_mb > 0) per = std::min(per, (g->tb_budget_mb << 20) / (int64_t)S);
-		tb_slot_bytes = std::max<int64_t>(4096, per) / 4 * 4;
-		if (ensure(g, g->tb, S * (size_t)tb_slot_bytes)) return -1;
-		if (ensure(g, g->row_off, S * (size_t)rows_slot * 8)) return -1;
-		if (ensure(g, g->row_lo, S * (size_t)rows_slot * 4)) return -1;
-		if (ensure(g, g->cig_scratch, S * (size_t)cig_scratch_slot * 4)) return -1;
-	}
+	Plan pl;
+	pl.kind = 3, pl.cigar = (opt.flag & MWF_F_CIGAR) != 0, pl.block = window_block(rq.group);
+	const int per_cu = cached_occupancy(g, P, pl, 0, false);
+	const int slots = std::max(1, std::min(rq.slots, g->n_cu * std::max(1, per_cu)));
+	pl.grid = std::max(1, std::min<int>(slots, rq.n_items));
+	if (size_slots(g, P, rq.group, pl.grid, pl.cigar, tb_worst(rq.group), false, pl.ws)) return -1;
 	if (getenv("MWF_DEBUG"))
-		fprintf(stderr, "[libmwf_hip] kernel kind 3: block %d, %d workgroup(s) per CU, %d slots, %d pairs; grid %d, traceback %lld B per slot\n", block, per_cu, slots, n_items, grid, (long long)tb_slot_bytes);
+		fprintf(stderr, "[libmwf_hip] kernel kind 3: block %d, %d workgroup(s) per CU, %d slots, %d pairs; grid %d, traceback %lld B per slot\n", pl.block, per_cu, slots, rq.n_items, pl.grid, (long long)pl.ws.tb_slot_bytes);
 
 	EndsArgs e;
 	memset(&e, 0, sizeof(e));
 	BatchArgs &a = e.b;
-	a.seqs = b->d_seqs, a.t_off = b->d_t_off, a.q_off = b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // (always the original bytes)
-	a.order = d_ids, a.n_pairs = n_items;
-	if (g->queue_clean && g->queue_next < kQueueSlots) a.queue = (int32_t*)g->queue.p + g->queue_next++;
-	else {
-		a.queue = (int32_t*)g->queue.p;
-		HIP_TRY(g, hipMemsetAsync(g->queue.p, 0, 4, g->stream)); // (stream order: the launch that used it last is complete by then)
-	}
-	a.pen = P;
-	a.want_cigar = cigar ? 1 : 0;
-	a.max_s = opt.max_s, a.max_iter = opt.max_iter;
-	a.debug_pair = -1;
-	a.ring = (int32_t*)g->ring.p, a.ring_slot_ints = ring_slot_ints, a.W = W;
-	a.good = (unsigned long long*)g->good.p, a.GW = GW;
-	a.tb = cigar ? (uint8_t*)g->tb.p : nullptr, a.tb_slot_bytes = tb_slot_bytes;
-	a.row_off = cigar ? (int64_t*)g->row_off.p : nullptr, a.row_lo = cigar ? (int32_t*)g->row_lo.p : nullptr, a.rows_slot = rows_slot;
-	a.cig_scratch = cigar ? (uint32_t*)g->cig_scratch.p : nullptr, a.cig_scratch_slot = cig_scratch_slot;
-	a.cig_pool = b->d_cig_pool, a.cig_head = b->d_cig_head, a.cig_pool_words = b->cig_pool_words;
-	a.out_s = b->d_s, a.out_iter = b->d_iter, a.out_ncig = b->d_ncig, a.out_cigoff = b->d_cigoff;
-	a.out_status = b->d_status, a.out_cells1 = b->d_cells1;
+	fill_args(a, g, b, opt, P, pl.cigar, pl.ws, false); // (always the original bytes)
+	a.order = rq.d_order, a.n_pairs = rq.n_items;
+	if (take_counter(g, a.queue)) return -1;
+	a.debug_pair = -1, a.out_dbg = nullptr;
 	e.t_beg = b->ends.t_beg, e.t_end = b->ends.t_end, e.q_beg = b->ends.q_beg, e.q_end = b->ends.q_end;
 	e.out_range = b->d_range, e.sub_t_off = b->d_sub_t_off, e.sub_q_off = b->d_sub_q_off, e.sub_tl = b->d_sub_tl, e.sub_ql = b->d_sub_ql;
-
-	if (timed) HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
-	std::shared_lock<std::shared_mutex> gate(g_dev_gate[g->device % kMaxDevices]); // not while a whole-device kernel runs
-	const int lrc = launch_ends(e, grid, block, g->stream);
-	gate.unlock();
-	if (lrc != 0) {
-		g->err = "kernel launch failed (ends-free)";
-		return -1;
-	}
-	b->last_grid = std::max(b->last_grid, grid);
-	if (timed) {
-		HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
-		g->ev_pending = true;
-	}
-	g->stats.n_launches += 1;
-	g->stats.grid = std::max(g->stats.grid, grid), g->stats.block = block, g->stats.kernel_kind = 3;
-	g->stats.packed = 0, g->stats.lowmem_two_pass = 0;
-	return 0;
+	if (ran_kind) *ran_kind = 3;
+	return launch_gated(g, b, rq, pl, 0, "kernel launch failed (ends-free)", [&] { return launch_ends(e, pl.grid, pl.block, g->stream); });
 }
 
 // ---- whole-device kernel ------------------------------------------------------------------------------------------------
@@ -546,15 +522,16 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	const bool cigar = (opt.flag & MWF_F_CIGAR) != 0, low_mem = cigar && opt.step > 0;
 	const int n_groups = (int)pairs.size();
 	if (n_groups < 1 || Gs < 1 || (int64_t)Gs * n_groups > coop_grid_limit(g)) { g->err = "whole-device kernel cannot be made resident"; return -1; }
-	int64_t len = 0, bound = 0, bound1 = 0;
+	GroupInfo M;
 	bool traced = false;
 	for (int32_t pair : pairs) {
-		len = std::max<int64_t>(len, (int64_t)b->h_tl[pair] + b->h_ql[pair]);
-		bound = std::max(bound, penalty_bound(opt, b->h_tl[pair], b->h_ql[pair], true));
-		bound1 = std::max(bound1, penalty_bound(opt, b->h_tl[pair], b->h_ql[pair], false));
+		M.add(b->h_tl[pair], b->h_ql[pair], penalty_bound(opt, b->h_tl[pair], b->h_ql[pair], true), penalty_bound(opt, b->h_tl[pair], b->h_ql[pair], false), 0);
 		traced |= b->debug_pair == pair;
 	}
-	const int32_t W = (int32_t)((len + 3 + 255) / 256 * 256 + 512), GW = W / 64 + 2;
+	const int64_t len = M.max_len, bound = M.max_bound, bound1 = M.max_bound1;
+	SlotSizes ws; // (per pair; the systolic passes below get their own ring and good-bit shapes, set_cols())
+	set_row_stride(ws, len);
+	ws.ring_slot_ints = (int64_t)P.nH * ws.W;
 	const int64_t TC = coop_chunk_slots(Gs);
 	const size_t NG = (size_t)n_groups;
 	const int sysP = g->sys_p, sysP2 = g->sys_p;
@@ -657,25 +634,14 @@ int run_coop_group(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, const
 	if (ensure(g, g->sys_park, NG * (size_t)sys_park_group * 4)) return -1;
 	BatchArgs a;
 	memset(&a, 0, sizeof(a));
-	a.seqs = b->d_seqs, a.t_off = b->alpha_active ? b->d_rt_off : b->d_t_off, a.q_off = b->alpha_active ? b->d_rq_off : b->d_q_off, a.tl = b->d_tl, a.ql = b->d_ql; // ("alpha_remap": class-1 pairs' offsets lead to their copies)
+	ws.rows_slot = rows_slot, ws.cig_scratch_slot = cig_scratch, ws.tb_slot_bytes = tb_bytes;
+	fill_args(a, g, b, opt, P, cigar, ws, b->alpha_active);
 	a.n_pairs = b->n;
-	a.pen = P;
-	a.want_cigar = cigar ? 1 : 0;
 	a.step = low_mem ? opt.step : 0;
-	a.max_s = opt.max_s, a.max_iter = opt.max_iter;
-	a.debug_pair = b->debug_pair;
-	a.ring = (int32_t*)g->ring.p, a.ring_slot_ints = (int64_t)P.nH * W, a.W = W;
-	a.good = (unsigned long long*)g->good.p, a.GW = GW;
-	a.tb = cigar ? (uint8_t*)g->tb.p : nullptr, a.tb_slot_bytes = tb_bytes;
-	a.row_off = cigar ? (int64_t*)g->row_off.p : nullptr, a.row_lo = cigar ? (int32_t*)g->row_lo.p : nullptr, a.rows_slot = rows_slot;
-	a.cig_scratch = cigar ? (uint32_t*)g->cig_scratch.p : nullptr, a.cig_scratch_slot = cig_scratch;
-	a.cig_pool = b->d_cig_pool, a.cig_head = b->d_cig_head, a.cig_pool_words = b->cig_pool_words;
 	a.seg = low_mem ? (int32_t*)g->seg.p : nullptr, a.seg_slot = seg_slot;
 	a.sring = two_pass ? (int32_t*)g->sys_sring.p : nullptr; // (provenance of the systolic kernel's private H rings: the same shape, set_cols())
 	a.snap = two_pass ? (int32_t*)g->snap.p : nullptr, a.snap_slot_ints = snap_slot_ints;
 	a.snap_meta = two_pass ? (int32_t*)g->snap_meta.p : nullptr, a.snap_meta_slot = snap_meta_slot;
-	a.out_s = b->d_s, a.out_iter = b->d_iter, a.out_ncig = b->d_ncig, a.out_cigoff = b->d_cigoff;
-	a.out_status = b->d_status, a.out_cells1 = b->d_cells1, a.out_dbg = b->d_dbg4;
 	a.dbg = traced && n_groups == 1 ? (int32_t*)g->dbg.p : nullptr; // the band trace is a single-pair diagnostic
 	a.dbg_cap = a.dbg ? (int32_t)(g->dbg.bytes / 8) : 0;
 	a.coop_pair = pairs[0];
@@ -855,7 +821,7 @@ static int route_whole_device(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t 
 	if (!coop_supported(P0)) { g->err = "whole-device kernel does not support these penalties"; return -2; }
 	if (n_cu_coop < 1) { g->err = "whole-device kernel cannot be made resident"; return -1; }
 	std::vector<int32_t> idx(b->h_order.begin(), b->h_order.end());
-	std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; }); // longest first
+	std::stable_sort(idx.begin(), idx.end(), longer_first(b));
 	for (size_t at = 0; at < idx.size();) {
 		const int64_t len0 = (int64_t)b->h_tl[idx[at]] + b->h_ql[idx[at]];
 		const int Gs = coop_group_size(n_cu_coop, len0, false, sys_owned_cols(g->sys_p, 4));
@@ -906,14 +872,9 @@ static void group_maxima(const mwf_gpu_batch_t *b, const std::vector<int8_t> &cl
 		const int64_t tl = b->h_tl[i], ql = b->h_ql[i], len = tl + ql;
 		const int c = cls[(size_t)i];
 		const PairInfo &pi = info[(size_t)i];
-		GroupInfo &G = cp.gi[c];
-		++G.n;
-		G.max_len = std::max(G.max_len, len), G.max_bound = std::max(G.max_bound, pi.bound);
-		G.max_bound1 = std::max(G.max_bound1, pi.bound1);
 		// (the mid class: the window its pairs are expected to reach, forced gap included — its launch picks the workgroup size by it)
 		const int64_t exp_win = row(c).geom == GEOM_MID ? std::min<int64_t>(len + 1, (int64_t)((double)len * div_r * 0.28) + 2 * std::abs(tl - ql)) : pi.exp_win;
-		G.max_tl = std::max<int64_t>(G.max_tl, tl), G.max_exp_win = std::max(G.max_exp_win, exp_win);
-		G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, ((tl + 3) & ~3LL) + 8 + ((ql + 3) & ~3LL) + 16);
+		cp.gi[c].add(tl, ql, pi.bound, pi.bound1, exp_win);
 	}
 }
 
@@ -971,9 +932,7 @@ static int order_pairs(mwf_gpu_t *g, mwf_gpu_batch_t *b, const std::vector<int8_
 	if (b->h_len_order.empty()) {
 		b->h_len_order.resize((size_t)b->n);
 		std::iota(b->h_len_order.begin(), b->h_len_order.end(), 0);
-		std::stable_sort(b->h_len_order.begin(), b->h_len_order.end(), [&](int32_t x, int32_t y) {
-			return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y];
-		});
+		std::stable_sort(b->h_len_order.begin(), b->h_len_order.end(), longer_first(b));
 	}
 	{
 		int32_t next[kNumClasses];
@@ -1087,6 +1046,17 @@ static int launch_classes(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt
 	return 0;
 }
 
+// what every align call resets: the batch's record of its last align and what was derived from that align's CIGARs, the engine's statistics
+static void begin_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, bool ends_free)
+{
+	b->opt = opt, b->ends_last = ends_free;
+	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
+	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
+	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
+	g->stats = mwf_gpu_stats_t{};
+	if (ends_free) g->stats.kernel_kind = 3;
+}
+
 } // namespace host
 } // namespace mwf
 
@@ -1097,12 +1067,7 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 	if (!g || !b || !opt) return -1;
 	if (const char *why = validate(*opt)) { g->err = why; return -2; }
 	(void)hipSetDevice(g->device);
-	b->opt = *opt;
-	b->ends_last = false;
-	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
-	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
-	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
-	g->stats = mwf_gpu_stats_t{};
+	begin_align(g, b, *opt, false);
 	if (b->n == 0) { b->aligned = b->finalized = true, b->alpha_known = g->alpha_remap != 0; return 0; } // (an empty batch: nothing to classify or copy, and with "alpha_remap" 1 its zero classes are known)
 	if (alpha_prepare(g, b)) return -1; // ("alpha_remap": classes and copies first — the plan below follows them)
 	if (place_results(g, b, (opt->flag & MWF_F_CIGAR) != 0)) return -1;
@@ -1148,16 +1113,11 @@ int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 	const Penalty P0 = make_penalty(*opt);
 	if (P0.nH > kMaxRing) { g->err = "ends-free alignment: max(x, o1+e1, o2+e2) must be < 256"; return -2; }
 	(void)hipSetDevice(g->device);
-	int64_t max_len = 0;
-	for (int32_t i = 0; i < b->n; ++i) max_len = std::max<int64_t>(max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
-	if (max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
-	b->opt = *opt, b->ends = *ends;
-	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
-	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false);
-	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
-	b->ends_last = true;
-	g->stats = mwf_gpu_stats_t{};
-	g->stats.kernel_kind = 3;
+	LaunchReq rq; // every pair, longest first, on as many workgroups as stay resident
+	for (int32_t i = 0; i < b->n; ++i) rq.group.add(b->h_tl[i], b->h_ql[i], penalty_bound(P0, opt->max_s, b->h_tl[i], b->h_ql[i], true), 0, 0);
+	if (rq.group.max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
+	begin_align(g, b, *opt, true);
+	b->ends = *ends;
 	if (b->n == 0) { b->aligned = b->finalized = true; return 0; }
 	const size_t N = (size_t)b->n;
 	if (!b->ends_buf.p) { // [range | sub_t_off | sub_q_off | sub_tl | sub_ql | order]
@@ -1177,10 +1137,8 @@ int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 	b->busy = true;
 	bool preset = false;
 	if (reset_results(g, b, was_busy, preset)) return -1;
-	GroupInfo G;
-	G.n = b->n, G.max_len = max_len;
-	for (int32_t i = 0; i < b->n; ++i) G.max_bound = std::max(G.max_bound, penalty_bound(P0, opt->max_s, b->h_tl[i], b->h_ql[i], true));
-	if (run_ends_kernel(g, b, b->d_ends_order, b->n, 1 << 30, G, true)) return -1;
+	rq.opt = *opt, rq.d_order = b->d_ends_order, rq.n_items = b->n, rq.timed_begin = rq.timed_end = true;
+	if (run_ends_kernel(g, b, rq, nullptr)) return -1;
 	std::fill(b->h_kind.begin(), b->h_kind.end(), (int8_t)3);
 	b->aligned = true;
 	return 0;
@@ -1191,255 +1149,217 @@ int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 namespace mwf {
 namespace host {
 
+// ---- after the launches: results, and the re-runs of what did not fit where it ran (the rule and the routes: mwf_plan_retry.h) --------------------------
 
-// Wait for the batch; re-run what did not fit where it ran:
-//   window outgrew a band kernel's span   -> the wide band kernel, from there the generic kernel
-//   traceback / snapshot arena too small  -> the same kernel on fewer workgroups (= larger slots)
-//   whole-device kernel: a pair that shared the device gets it alone; the arena grows while memory lasts; a wait that
-//   gave up (workgroups not resident) or a window beyond the device's span falls back to the generic kernel.
+// The fixed-size results, once the batch's kernels are through: into b->host_out and from there into h_status, h_s, h_ncig, h_iter, h_cigoff, h_cells1.
+static int fetch_results(mwf_gpu_t *g, mwf_gpu_batch_t *b)
+{
+	const size_t n = (size_t)b->n;
+	std::vector<char> &host = b->host_out;
+	const BlockLayout L = layout_block(n, 0, false); // (only differences between result offsets are used)
+	// a score-only, high-memory align: n_cigar, CIGAR offsets and first-pass cells are zero by construction — only head, status, s and
+	// n_iter come back (16 of the 36 bytes per pair)
+	const bool lean = !(b->opt.flag & MWF_F_CIGAR);
+	const size_t need = lean ? b->out_bytes_score : b->out_bytes;
+	if (n == 0) { HIP_TRY(g, hipStreamSynchronize(g->stream)); return 0; }
+	b->h_cig_valid = false;
+	if (b->out_in_pin) { // the kernels wrote the engine's pinned result page (score-only: no CIGAR words)
+		HIP_TRY(g, hipStreamSynchronize(g->stream));
+		memcpy(host.data(), g->res_pin, b->out_bytes);
+		memset(host.data(), 0, 8);
+	} else if (lean) {
+		if (download(g, host.data(), (const char*)b->block.p + b->out_off, need)) return -1;
+		memset(host.data() + need, 0, b->out_bytes - need);
+	} else {
+		// a small CIGAR-mode batch (the single pair of a drop-in call): the head of its CIGAR pool comes back with the results, one wait
+		// for both copies — when the pool's used part turns out to fit it, fetch_cigars() has nothing left to copy
+		const size_t spec = (b->opt.flag & MWF_F_CIGAR) && b->d_cig_pool && n <= 64 ? (size_t)std::min<int64_t>(b->cig_pool_words, 1024) : 0;
+		const size_t cig_at = align_up(b->out_bytes, 64);
+		if (spec > 0 && pin_reserve(g, cig_at + spec * 4) == 0) {
+			HIP_TRY(g, hipMemcpyAsync(g->pin, (const char*)b->block.p + b->out_off, b->out_bytes, hipMemcpyDeviceToHost, g->stream));
+			HIP_TRY(g, hipMemcpyAsync((char*)g->pin + cig_at, b->d_cig_pool, spec * 4, hipMemcpyDeviceToHost, g->stream));
+			HIP_TRY(g, hipStreamSynchronize(g->stream));
+			g->pin_busy[0] = g->pin_busy[1] = false;
+			memcpy(host.data(), g->pin, b->out_bytes);
+			unsigned long long used = 0;
+			memcpy(&used, host.data(), 8);
+			if (used <= spec) {
+				b->h_cig.assign((const uint32_t*)((const char*)g->pin + cig_at), (const uint32_t*)((const char*)g->pin + cig_at) + used);
+				b->h_cig_valid = true; // (a re-run fetches again and decides again)
+			}
+		} else if (download(g, host.data(), (const char*)b->block.p + b->out_off, b->out_bytes)) return -1;
+	}
+	const char *o = host.data() - L.head;
+	memcpy(&b->cig_used, o + L.head, 8);
+	b->cig_used = std::min<int64_t>(b->cig_used, b->cig_pool_words); // (the head advances in whole blocks: its last step may point past the pool)
+	memcpy(b->h_status.data(), o + L.status, n * 4), memcpy(b->h_s.data(), o + L.s, n * 4), memcpy(b->h_ncig.data(), o + L.ncig, n * 4);
+	memcpy(b->h_iter.data(), o + L.iter, n * 8), memcpy(b->h_cigoff.data(), o + L.cigoff, n * 8), memcpy(b->h_cells1.data(), o + L.cells1, n * 8);
+	return 0;
+}
+
+// pairs a follow-up launch re-ran from the device-side list count as re-runs too (the third word of the head: BatchArgs::retry_count)
+static void count_device_retries(mwf_gpu_batch_t *b)
+{
+	if (!b->dev_retry_used) return;
+	for (int slot = 0; slot < kRetrySlots; ++slot) { // (what a list could not hold stayed ST_BAND_OVERFLOW and is counted by the host path)
+		uint32_t k = 0;
+		memcpy(&k, b->host_out.data() + 16 + 8 * slot, 4);
+		b->n_retries += (int32_t)std::min<uint32_t>(k, (uint32_t)kRetryCap);
+	}
+}
+
+// the four-slot kernels' report (reset to 0 by the align's reset kernel): did any pair need more than three slots hold?
+static void note_wide_slots(mwf_gpu_batch_t *b)
+{
+	if (!b->plan.wide_measured) return;
+	uint32_t aux = 0;
+	memcpy(&aux, b->host_out.data() + 8, 4);
+	if (b->plan.wide_state == 0) b->plan.wide_state = (aux & 1u) ? 2 : 1;
+	b->plan.wide_measured = false;
+}
+
+static bool low_mem_call(const mwf_opt_t &o) { return (o.flag & MWF_F_CIGAR) && o.step > 0; }
+
+// the pair lists of one round of re-runs: [route][step0 index]
+struct RetryLists {
+	std::vector<int32_t> ids[kNumRoutes][2];
+	size_t n = 0;                           // pairs on them
+	bool grow_coop = false, fewer = false;  // a pair asked for a larger whole-device arena; a fewer-slots list has pairs
+};
+
+// Route every unfinished pair: the rule's decision applied — the pair's new class and flags, the wide class's state, the warnings — and the pair on its list.
+// -3 / -4: a pair that no re-run can finish.
+static int route_unfinished(mwf_gpu_t *g, mwf_gpu_batch_t *b, const RetryRule &R, int round, bool &coop_warned, RetryLists &L)
+{
+	static const bool dbg_route = getenv("MWF_DEBUG_REROUTE") != nullptr; // (diagnostics: why a pair is run again)
+	const size_t n = (size_t)b->n;
+	for (size_t i = 0; i < n; ++i) {
+		const int32_t st = b->h_status[i];
+		if (st == ST_OK || st == ST_STOPPED) continue;
+		const int kind = b->h_kind[i];
+		if (dbg_route) fprintf(stderr, "[libmwf_hip] re-route: pair %zu (tl %d ql %d) status %d kind %d class %d flags %d n_iter word %lld round %d\n", i, b->h_tl[i], b->h_ql[i], st, kind, (int)b->h_class[i], (int)b->h_flags[i], (long long)b->h_iter[i], round);
+		const RouteDecision d = reroute_pair(R, PairState{b->h_tl[i], b->h_ql[i], st, (int8_t)kind, b->h_class[i], b->h_flags[i], b->h_iter[i]});
+		if (d.route == ROUTE_FAIL_STATUS) {
+			g->err = "pair " + std::to_string(i) + " failed on the device with status " + std::to_string(st) + (kind == 3 ? " (ends-free)" : "");
+			return -3;
+		}
+		if (is_failure(d.route)) {
+			g->err = std::string(d.route == ROUTE_FAIL_TB ? "traceback" : "low-memory snapshots") + " of pair " + std::to_string(i) + " (tl=" + std::to_string(b->h_tl[i]) + ", ql=" + std::to_string(b->h_ql[i]) +
+			         ") do not fit in device memory" + (b->opt.step > 0 || kind == 3 ? "" : "; set opt.step > 0 (low-memory mode)");
+			return -4;
+		}
+		if (d.warn == WARN_COOP_GAVE_UP) fprintf(stderr, "[libmwf_hip] warning: whole-device kernel gave up waiting for a workgroup on pair %d; re-running it on one workgroup (slow)\n", (int)i);
+		if (d.warn == WARN_COOP_SPAN && !coop_warned) fprintf(stderr, "[libmwf_hip] warning: wavefront of pair %d outgrew the whole-device kernel's span; re-running it on one workgroup (slow)\n", (int)i), coop_warned = true;
+		if (d.wide_needs_four) b->plan.wide_state = 2;
+		b->h_class[i] = d.h_class, b->h_flags[i] = d.h_flags;
+		L.grow_coop |= d.grow_coop, L.fewer |= takes_fewer_slots(d.route), ++L.n;
+		L.ids[d.route][d.step0].push_back((int32_t)i);
+	}
+	return 0;
+}
+
+// One list on its route's launch function: longest pair first, the maxima, the ids into g->retry_ids (the previous re-run's kernels are through: every list ends with
+// a stream synchronisation), the launch, the wait for it; h_kind gets the kernel that ran.
+static int run_list(mwf_gpu_t *g, mwf_gpu_batch_t *b, std::vector<int32_t> &ids, const RouteRow &T, int step0, int slots, Geom geom, CopyForm copy)
+{
+	if (ids.empty()) return 0;
+	int64_t hint = 0;
+	if (T.use_forecast) { // every pair of the re-run came back with a forecast: the class that holds the widest of them (+ 25 %)
+		for (int32_t i : ids) {
+			if (b->h_iter[i] >= 0) { hint = 0; break; }
+			hint = std::max<int64_t>(hint, -b->h_iter[i] * 5 / 4 + 64);
+		}
+		// (every forecast of this re-run is at most kBandWide4Window: the margin must not push the hint past the four-slot geometry, back onto three slots)
+		if (hint > kBandWide4Window && T.want_kind == 2 && geom == GEOM_CHOOSE) hint = kBandWide4Window;
+	}
+	std::stable_sort(ids.begin(), ids.end(), longer_first(b));
+	LaunchReq rq;
+	rq.opt = b->opt;
+	if (step0) rq.opt.step = 0;
+	const mwf_opt_t &o = rq.opt;
+	for (int32_t i : ids) rq.group.add(b->h_tl[i], b->h_ql[i], penalty_bound(o, b->h_tl[i], b->h_ql[i], true), penalty_bound(o, b->h_tl[i], b->h_ql[i], false), 0);
+	const GroupInfo &G = rq.group;
+	DevBuf &tmp = g->retry_ids;
+	if (ensure(g, tmp, std::max<size_t>(ids.size() * 4, 4096))) return -1;
+	if (upload_segments(g, (char*)tmp.p, std::vector<Seg>{Seg{ids.data(), ids.size() * 4}})) return -1;
+	// a handful of short pairs that outgrew the lane kernel (one read in tens of thousands): the mid kernel, whose span holds the widest
+	// window such a pair can have at all, takes a fraction of what a lone workgroup of the band classes takes (one 150 bp pair: 0.18 ms
+	// of band kernel in every align of the 40 000-pair batch, profiles/r04/rocprof_lane_kernel_40000x150bp.txt)
+	const int mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
+	const bool to_mid = T.want_kind == 2 && T.use_forecast && copy != COPY_NIB && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(make_penalty(o)) && G.max_len <= 1200 &&
+	                    G.max_tl + G.max_bound < 32760 && !low_mem_call(o);
+	rq.d_order = (const int32_t*)tmp.p, rq.n_items = G.n, rq.slots = slots;
+	rq.geom = to_mid ? GEOM_MID : geom, rq.copy = copy, rq.want_kind = T.want_kind, rq.window_hint = hint, rq.ring16_allowed = T.ring16_allowed;
+	// (a re-run whose forecast is clamped to the four-slot window asks for the report as the wide class's measuring launch does, as it always has: nothing reads
+	// the word after a re-run — finalize() looked at it before, and the next align's reset kernel zeroes it)
+	rq.report_wide = rq.geom == GEOM_CHOOSE && hint == kBandWide4Window;
+	int ran = 0;
+	if (T.launch == LAUNCH_ENDS ? run_ends_kernel(g, b, rq, &ran) : run_batch_kernel(g, b, rq, &ran)) return -1;
+	if (hipStreamSynchronize(g->stream) != hipSuccess) return -1;
+	for (int32_t i : ids) b->h_kind[i] = (int8_t)ran;
+	return 0;
+}
+
+// The lists of one round: for each of the two step0 indices, kRouteTable's order (the whole-device and ends-free lists hold their pairs under index 0); every launch
+// as its route's row says.
+static int run_routes(mwf_gpu_t *g, mwf_gpu_batch_t *b, RetryLists &L, int grid0, int tb_slots)
+{
+	// (as the plan's nib_pair: the pair's copy holds image bytes and the set has 4-bit kernels — a re-run respects the class)
+	const bool nib_on = g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(make_penalty(b->opt)) && !low_mem_call(b->opt);
+	for (int z = 0; z < 2; ++z)
+		for (int r = 0; r < kNumRoutes; ++r) {
+			const RouteRow &T = kRouteTable[r];
+			std::vector<int32_t> &ids = L.ids[r][z];
+			if (ids.empty()) continue;
+			if (T.launch == LAUNCH_COOP) {
+				for (int32_t i : ids)
+					if (run_coop_pair(g, b, b->opt, i, false, false)) return -1;
+				continue;
+			}
+			const int slots = T.slots == SLOTS_GRID0 ? grid0 : T.slots == SLOTS_ALL ? 1 << 30 : std::max(1, std::min<int>(tb_slots, (int)ids.size()));
+			const bool all_span = T.span_if_all && std::all_of(ids.begin(), ids.end(), [&](int32_t i) { return b->h_class[i] == CLS_SPAN; });
+			const Geom geom = all_span ? GEOM_SPAN : T.geom;
+			if (!T.nib_split || (z == 0 && low_mem_call(b->opt))) { // (index 1 runs as high-memory)
+				if (run_list(g, b, ids, T, z, slots, geom, T.copy)) return -1;
+				continue;
+			}
+			// a band re-run on sequence copies: the class-3 pairs of the list ("alpha16") apart from the rest, on the 4-bit form of the same geometry
+			std::vector<int32_t> nib_ids, rest;
+			for (int32_t i : ids) (nib_on && (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3 ? nib_ids : rest).push_back(i);
+			if (run_list(g, b, rest, T, z, slots, geom, COPY_2BIT) || run_list(g, b, nib_ids, T, z, slots, geom, COPY_NIB)) return -1;
+		}
+	return 0;
+}
+
+// Wait for the batch; re-run what did not fit where it ran, in at most 16 rounds (a round whose fewer-slots lists have pairs leaves them an eighth of the workgroups).
 int finalize(mwf_gpu_t *g, mwf_gpu_batch_t *b)
 {
 	if (b->finalized) return 0;
 	if (!b->aligned) { g->err = "batch was not aligned"; return -1; }
 	const size_t n = (size_t)b->n;
 	b->h_s.resize(n), b->h_ncig.resize(n), b->h_status.resize(n), b->h_iter.resize(n), b->h_cigoff.resize(n), b->h_cells1.resize(n);
-	std::vector<char> &host = b->host_out;
-	if (host.size() < b->out_bytes) host.resize(b->out_bytes);
-	const BlockLayout L = layout_block(n, 0, false); // (only differences between result offsets are used)
-	// a score-only, high-memory align: n_cigar, CIGAR offsets and first-pass cells are zero by construction — only head, status, s and
-	// n_iter come back (16 of the 36 bytes per pair)
-	const bool lean = !(b->opt.flag & MWF_F_CIGAR);
-	const size_t need = lean ? b->out_bytes_score : b->out_bytes;
-	auto fetch = [&]() -> int {
-		if (n == 0) { HIP_TRY(g, hipStreamSynchronize(g->stream)); return 0; }
-		if (b->out_in_pin) { // the kernels wrote the engine's pinned result page (score-only: no CIGAR words)
-			HIP_TRY(g, hipStreamSynchronize(g->stream));
-			memcpy(host.data(), g->res_pin, b->out_bytes);
-			memset(host.data(), 0, 8);
-			b->h_cig_valid = false;
-		} else if (lean) {
-			b->h_cig_valid = false;
-			if (download(g, host.data(), (const char*)b->block.p + b->out_off, need)) return -1;
-			memset(host.data() + need, 0, b->out_bytes - need);
-		} else {
-			// a small CIGAR-mode batch (the single pair of a drop-in call): the head of its CIGAR pool comes back with the results, one wait
-			// for both copies — when the pool's used part turns out to fit it, fetch_cigars() has nothing left to copy
-			const size_t spec = (b->opt.flag & MWF_F_CIGAR) && b->d_cig_pool && n <= 64 ? (size_t)std::min<int64_t>(b->cig_pool_words, 1024) : 0;
-			const size_t cig_at = align_up(b->out_bytes, 64);
-			b->h_cig_valid = false;
-			if (spec > 0 && pin_reserve(g, cig_at + spec * 4) == 0) {
-				HIP_TRY(g, hipMemcpyAsync(g->pin, (const char*)b->block.p + b->out_off, b->out_bytes, hipMemcpyDeviceToHost, g->stream));
-				HIP_TRY(g, hipMemcpyAsync((char*)g->pin + cig_at, b->d_cig_pool, spec * 4, hipMemcpyDeviceToHost, g->stream));
-				HIP_TRY(g, hipStreamSynchronize(g->stream));
-				g->pin_busy[0] = g->pin_busy[1] = false;
-				memcpy(host.data(), g->pin, b->out_bytes);
-				unsigned long long used = 0;
-				memcpy(&used, host.data(), 8);
-				if (used <= spec) {
-					b->h_cig.assign((const uint32_t*)((const char*)g->pin + cig_at), (const uint32_t*)((const char*)g->pin + cig_at) + used);
-					b->h_cig_valid = true; // (a re-run below fetches again and decides again)
-				}
-			} else if (download(g, host.data(), (const char*)b->block.p + b->out_off, b->out_bytes)) return -1;
-		}
-		const char *o = host.data() - L.head;
-		memcpy(&b->cig_used, o + L.head, 8);
-		b->cig_used = std::min<int64_t>(b->cig_used, b->cig_pool_words); // (the head advances in whole blocks: its last step may point past the pool)
-		memcpy(b->h_status.data(), o + L.status, n * 4), memcpy(b->h_s.data(), o + L.s, n * 4), memcpy(b->h_ncig.data(), o + L.ncig, n * 4);
-		memcpy(b->h_iter.data(), o + L.iter, n * 8), memcpy(b->h_cigoff.data(), o + L.cigoff, n * 8), memcpy(b->h_cells1.data(), o + L.cells1, n * 8);
-		return 0;
-	};
-	if (fetch()) return -1;
-	if (b->dev_retry_used) { // pairs a follow-up launch re-ran from the device-side list count as re-runs too (the third word of the head: BatchArgs::retry_count)
-		for (int slot = 0; slot < kRetrySlots; ++slot) { // (what a list could not hold stayed ST_BAND_OVERFLOW and is counted by the host path below)
-			uint32_t k = 0;
-			memcpy(&k, b->host_out.data() + 16 + 8 * slot, 4);
-			b->n_retries += (int32_t)std::min<uint32_t>(k, (uint32_t)kRetryCap);
-		}
-	}
-
-	if (b->plan.wide_measured) { // the four-slot kernels' report (reset to 0 by the align's reset kernel): did any pair need more than three slots hold?
-		uint32_t aux = 0;
-		memcpy(&aux, host.data() + 8, 4);
-		if (b->plan.wide_state == 0) b->plan.wide_state = (aux & 1u) ? 2 : 1;
-		b->plan.wide_measured = false;
-	}
+	if (b->host_out.size() < b->out_bytes) b->host_out.resize(b->out_bytes);
+	if (fetch_results(g, b)) return -1;
+	count_device_retries(b);
+	note_wide_slots(b);
 	b->busy = false;
-	mwf_opt_t opt_hi = b->opt;
-	opt_hi.step = 0;
+	RetryRule R;
+	R.band_span = g->band_span, R.seq2bit = g->seq2bit, R.force_kind = g->force_kind, R.block = g->block, R.tb_budget_mb = g->tb_budget_mb;
+	R.step = b->opt.step, R.span_window = band_span_window();
+	R.coop_can_grow = [](void *ctx) { return coop_can_grow((mwf_gpu_t*)ctx); }, R.ctx = g;
 	int tb_slots = std::max(1, b->last_grid);
-	const int grid0 = std::max(1, b->last_grid);
+	const int grid0 = tb_slots;
 	bool coop_warned = false;
-	const char *fail = nullptr;
-	for (int round = 0; round < 16 && !fail; ++round) {
-		// where every unfinished pair goes next: route = kind (0 generic, 1 whole-device alone, 2 band) and, for the band kernel, the class
-		std::vector<int32_t> to_generic[2], to_generic32[2], to_band_wide[2], to_band_span[2], to_band_bytes[2], same_fewer[3][2], coop_alone, ends_fewer;
-		bool grow_coop = false;
-		for (size_t i = 0; i < n; ++i) {
-			const int32_t st = b->h_status[i];
-			if (st == ST_OK || st == ST_STOPPED) continue;
-			const int kind = b->h_kind[i], step0 = b->h_flags[i] & FLAG_STEP0;
-			static const bool dbg_route = getenv("MWF_DEBUG_REROUTE") != nullptr; // (diagnostics: why a pair is run again)
-			if (dbg_route) fprintf(stderr, "[libmwf_hip] re-route: pair %zu (tl %d ql %d) status %d kind %d class %d flags %d n_iter word %lld round %d\n", i, b->h_tl[i], b->h_ql[i], st, kind, (int)b->h_class[i], (int)b->h_flags[i], (long long)b->h_iter[i], round);
-			if (kind == 3 && st == ST_TB_OVERFLOW) { // an ends-free pair only ever runs on its own kernel: again on fewer workgroups (= larger slots)
-				if (tb_slots == 1) fail = "traceback"; // already had the whole budget
-				ends_fewer.push_back((int32_t)i);
-			} else if (kind == 3) {
-				g->err = "pair " + std::to_string(i) + " failed on the device with status " + std::to_string(st) + " (ends-free)";
-				return -3;
-			} else if (st == ST_BAND_OVERFLOW && kind == 0) {
-				to_generic32[step0].push_back((int32_t)i); // an offset outgrew the generic kernel's 16-bit ring rows: 32-bit rows
-			} else if (st == ST_ALPHABET && kind == 2 && b->h_class[i] == CLS_SPAN) {
-				b->h_class[i] = CLS_GENERIC, to_generic[step0].push_back((int32_t)i); // (the span geometry has no byte-wise form)
-			} else if (st == ST_ALPHABET && kind == 2) {
-				to_band_bytes[step0].push_back((int32_t)i); // not plain ACGT: the byte-wise band kernel of the same class
-			} else if (st == ST_BAND_OVERFLOW && kind == 2) {
-				// (a pair handed back EARLY carries the window it is expected to need, negated, where n_iter would be: one that no band class
-				// holds goes straight to the generic kernel)
-				const int64_t est = b->h_iter[i] < 0 ? -b->h_iter[i] : 0;
-				// (a pair of the wide class that outgrew its three chunk slots per wave LATE — that geometry carries no forecast — is re-run alone, ~7 ms for a
-				// 10 kb pair beside the batch's 17: the next align of this batch takes the four-slot geometry for the class)
-				// (only a pair that really ran on that geometry says so: CLS_BIASED pairs on biased offsets and re-runs of mid / lane pairs carry CLS_WIDE as well)
-				if ((b->h_flags[i] & FLAG_THREE_SLOTS) && est == 0) b->plan.wide_state = 2;
-				b->h_flags[i] &= ~FLAG_THREE_SLOTS;
-				// (... only when the forecast is half again beyond the widest class: it is an estimate, and the generic kernel is several times slower)
-				// what outgrew (or is forecast to outgrow) the 512-thread geometry: the 1024-thread span geometry, if the pair fits that
-				const bool span_ok = is_band_size_class(b->h_class[i]) && g->band_span != 0 && g->seq2bit != 0 && g->force_kind < 0 && g->block == 0 &&
-				                     b->h_tl[i] <= kBandSpanMaxSeq && b->h_ql[i] <= kBandSpanMaxSeq && est <= band_span_window();
-				// (a forecast the four-slot 512-thread geometry holds — the re-run takes four slots for it, see rerun(); beyond it the span geometry at once:
-				// round 4 sent forecasts of up to 1.5 x the THREE-slot window here and re-ran them on three slots, which by their own forecast could not hold them)
-				// (every class but generic and wide: a pair of the span geometry whose forecast is that small takes this way too, as it always has)
-				if (b->h_class[i] != CLS_GENERIC && b->h_class[i] != CLS_WIDE && est <= kBandWide4Window) b->h_class[i] = CLS_WIDE, to_band_wide[step0].push_back((int32_t)i);
-				else if (span_ok) b->h_class[i] = CLS_SPAN, to_band_span[step0].push_back((int32_t)i);
-				// (a forecast also says whether the generic kernel's 16-bit ring rows can hold the pair — offsets up to 65 532, i.e. target length
-				// + final penalty, about half the window: 50 kb pairs at 15 % ran them for nothing before taking the 32-bit rows)
-				else if (est > 0 && (int64_t)b->h_tl[i] + est / 2 + 64 > 65000) b->h_class[i] = CLS_GENERIC, to_generic32[step0].push_back((int32_t)i);
-				else b->h_class[i] = CLS_GENERIC, to_generic[step0].push_back((int32_t)i);
-			} else if (kind == 1 && st == ST_INTERNAL && !(b->h_flags[i] & FLAG_COOP_GAVE_UP)) {
-				// a wait between workgroups of the whole-device kernel ran into its spin limit (they were not all resident, e.g.
-				// the device is shared): the one-workgroup kernel needs no such thing
-				fprintf(stderr, "[libmwf_hip] warning: whole-device kernel gave up waiting for a workgroup on pair %d; re-running it on one workgroup (slow)\n", (int)i);
-				b->h_flags[i] |= FLAG_COOP_GAVE_UP;
-				to_generic[step0].push_back((int32_t)i);
-			} else if (kind == 1 && (st == ST_BAND_OVERFLOW || st == ST_TB_OVERFLOW || st == ST_SNAP_OVERFLOW)) {
-				if (b->h_flags[i] & FLAG_COOP_SHARED) coop_alone.push_back((int32_t)i); // had a share of the workgroups and of the arena: now alone
-				else if (st == ST_BAND_OVERFLOW && (b->h_flags[i] & FLAG_COOP_NARROW) && !(b->h_flags[i] & FLAG_COOP_WIDE)) {
-					b->h_flags[i] |= FLAG_COOP_WIDE; // its window outgrew the 64-column slots: again with 256-column ones
-					coop_alone.push_back((int32_t)i);
-				} else if (st == ST_BAND_OVERFLOW) {
-					if (!coop_warned) fprintf(stderr, "[libmwf_hip] warning: wavefront of pair %d outgrew the whole-device kernel's span; re-running it on one workgroup (slow)\n", (int)i);
-					coop_warned = true;
-					to_generic[step0].push_back((int32_t)i);
-				} else if (g->tb_budget_mb == 0 && g->coop_tb_mult < ((int64_t)1 << 20) && coop_can_grow(g)) grow_coop = true, coop_alone.push_back((int32_t)i);
-				else if (b->opt.step > 0 && !step0) to_generic[0].push_back((int32_t)i); // the first-pass traceback does not fit: true two-pass mode
-				else fail = "traceback";
-			} else if (st == ST_TB_OVERFLOW || st == ST_SNAP_OVERFLOW) {
-				if (tb_slots == 1) fail = st == ST_TB_OVERFLOW ? "traceback" : "low-memory snapshots"; // already had the whole budget
-				same_fewer[kind == 2 ? 2 : 0][step0].push_back((int32_t)i);
-			} else {
-				g->err = "pair " + std::to_string(i) + " failed on the device with status " + std::to_string(st);
-				return -3;
-			}
-			if (fail) {
-				g->err = std::string(fail) + " of pair " + std::to_string(i) + " (tl=" + std::to_string(b->h_tl[i]) + ", ql=" + std::to_string(b->h_ql[i]) +
-				         ") do not fit in device memory" + (b->opt.step > 0 || kind == 3 ? "" : "; set opt.step > 0 (low-memory mode)");
-				return -4;
-			}
-		}
-		size_t n_redo = coop_alone.size() + ends_fewer.size();
-		for (int z = 0; z < 2; ++z) n_redo += to_generic[z].size() + to_generic32[z].size() + to_band_wide[z].size() + to_band_span[z].size() + to_band_bytes[z].size() + same_fewer[0][z].size() + same_fewer[2][z].size();
-		if (n_redo == 0) break;
-		b->n_retries += (int32_t)n_redo;
-		if (grow_coop) g->coop_tb_mult *= 2;
-		for (int32_t i : coop_alone)
-			if (run_coop_pair(g, b, b->opt, i, false, false)) return -1;
-		const bool shrink = !same_fewer[0][0].empty() || !same_fewer[0][1].empty() || !same_fewer[2][0].empty() || !same_fewer[2][1].empty() || !ends_fewer.empty();
-		if (shrink) tb_slots = std::max(1, tb_slots / 8);
-		if (!ends_fewer.empty()) { // (an ends-free batch has no other list)
-			std::stable_sort(ends_fewer.begin(), ends_fewer.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; });
-			mwf_gpu_batch_t::PlanCache::GI G;
-			for (int32_t i : ends_fewer) {
-				G.max_len = std::max<int64_t>(G.max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
-				G.max_bound = std::max(G.max_bound, penalty_bound(b->opt, b->h_tl[i], b->h_ql[i], true));
-			}
-			G.n = (int32_t)ends_fewer.size();
-			DevBuf &tmp = g->retry_ids;
-			if (ensure(g, tmp, std::max<size_t>(ends_fewer.size() * 4, 4096))) return -1;
-			if (upload_segments(g, (char*)tmp.p, std::vector<Seg>{Seg{ends_fewer.data(), ends_fewer.size() * 4}})) return -1;
-			if (run_ends_kernel(g, b, (const int32_t*)tmp.p, G.n, std::max(1, std::min<int>(tb_slots, G.n)), G, false)) return -1;
-			if (hipStreamSynchronize(g->stream) != hipSuccess) return -1;
-		}
-		auto pl_low_mem = [](const mwf_opt_t &o) { return (o.flag & MWF_F_CIGAR) && o.step > 0; };
-		const Penalty Pn = make_penalty(b->opt);
-		auto nib_pair = [&](int32_t i) { // (as the plan's: the pair's copy holds image bytes and the set has 4-bit kernels — a re-run respects the class)
-			return g->alpha16 != 0 && b->alpha_active && g->seq2bit != 0 && g->band_pack != 0 && g->band_span != 0 && band2_nib_supported(Pn) && !pl_low_mem(b->opt) &&
-			       (size_t)i < b->h_alpha.size() && b->h_alpha[(size_t)i] == 3;
-		};
-		auto rerun1 = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast, Geom geom, CopyForm copy, bool ring16_allowed) -> int {
-			if (ids.empty()) return 0;
-			int64_t hint = 0;
-			if (use_forecast) { // every pair of the re-run came back with a forecast: the class that holds the widest of them (+ 25 %)
-				for (int32_t i : ids) {
-					if (b->h_iter[i] >= 0) { hint = 0; break; }
-					hint = std::max<int64_t>(hint, -b->h_iter[i] * 5 / 4 + 64);
-				}
-				// (every forecast of this re-run is at most kBandWide4Window: the margin must not push the hint past the four-slot geometry, back onto three slots)
-				if (hint > kBandWide4Window && want_kind == 2 && geom == GEOM_CHOOSE) hint = kBandWide4Window;
-			}
-			std::stable_sort(ids.begin(), ids.end(), [&](int32_t x, int32_t y) { return (int64_t)b->h_tl[x] + b->h_ql[x] > (int64_t)b->h_tl[y] + b->h_ql[y]; });
-			const mwf_opt_t &o = step0 ? opt_hi : b->opt;
-			GroupInfo G;
-			for (int32_t i : ids) {
-				G.max_len = std::max<int64_t>(G.max_len, (int64_t)b->h_tl[i] + b->h_ql[i]);
-				G.max_bound = std::max(G.max_bound, penalty_bound(o, b->h_tl[i], b->h_ql[i], true));
-				G.max_bound1 = std::max(G.max_bound1, penalty_bound(o, b->h_tl[i], b->h_ql[i], false));
-				G.max_tl = std::max<int64_t>(G.max_tl, b->h_tl[i]);
-				G.max_seq_lds = std::max<int64_t>(G.max_seq_lds, (((int64_t)b->h_tl[i] + 3) & ~3LL) + 8 + (((int64_t)b->h_ql[i] + 3) & ~3LL) + 16);
-			}
-			G.n = (int32_t)ids.size();
-			DevBuf &tmp = g->retry_ids; // the ids of this re-run (the previous re-run's kernels are through: every rerun() ends with a stream synchronisation)
-			if (ensure(g, tmp, std::max<size_t>(ids.size() * 4, 4096))) return -1;
-			int rc = upload_segments(g, (char*)tmp.p, std::vector<Seg>{Seg{ids.data(), ids.size() * 4}});
-			int ran = 0;
-			// a handful of short pairs that outgrew the lane kernel (one read in tens of thousands): the mid kernel, whose span holds the widest
-			// window such a pair can have at all, takes a fraction of what a lone workgroup of the band classes takes (one 150 bp pair: 0.18 ms
-			// of band kernel in every align of the 40 000-pair batch, profiles/r04/rocprof_lane_kernel_40000x150bp.txt)
-			const Penalty Pm = make_penalty(o);
-			const int mid_cap = g->mid_max_pairs < 0 ? g->n_cu : g->mid_max_pairs;
-			const bool to_mid = want_kind == 2 && use_forecast && copy != COPY_NIB && g->force_kind < 0 && g->block == 0 && (int)ids.size() <= mid_cap && mid_supported(Pm) && G.max_len <= 1200 &&
-			                    G.max_tl + G.max_bound < 32760 && !(pl_low_mem(o));
-			LaunchReq rq;
-			rq.opt = o, rq.d_order = (const int32_t*)tmp.p, rq.n_items = G.n, rq.slots = slots, rq.group = G;
-			rq.geom = to_mid ? GEOM_MID : geom, rq.copy = copy, rq.want_kind = want_kind, rq.window_hint = hint, rq.ring16_allowed = ring16_allowed;
-			// (a re-run whose forecast is clamped to the four-slot window asks for the report as the wide class's measuring launch does, as it always has: nothing reads
-			// the word after a re-run — finalize() looked at it before, and the next align's reset kernel zeroes it)
-			rq.report_wide = rq.geom == GEOM_CHOOSE && hint == kBandWide4Window;
-			if (rc == 0) rc = run_batch_kernel(g, b, rq, &ran);
-			if (rc == 0) rc = hipStreamSynchronize(g->stream) == hipSuccess ? 0 : -1;
-			if (rc) return -1;
-			for (int32_t i : ids) b->h_kind[i] = (int8_t)ran;
-			return 0;
-		};
-		// a band re-run on sequence copies: the class-3 pairs of the list ("alpha16") apart from the rest, on the 4-bit form of the same geometry
-		auto rerun = [&](std::vector<int32_t> &ids, int step0, int want_kind, int slots, bool use_forecast = false, Geom geom = GEOM_CHOOSE, CopyForm copy = COPY_2BIT, bool ring16_allowed = true) -> int {
-			if (want_kind != 2 || copy == COPY_BYTES || pl_low_mem(step0 ? opt_hi : b->opt)) return rerun1(ids, step0, want_kind, slots, use_forecast, geom, copy, ring16_allowed);
-			std::vector<int32_t> nib_ids, rest;
-			for (int32_t i : ids) (nib_pair(i) ? nib_ids : rest).push_back(i);
-			if (rerun1(rest, step0, want_kind, slots, use_forecast, geom, COPY_2BIT, ring16_allowed)) return -1;
-			return rerun1(nib_ids, step0, want_kind, slots, use_forecast, geom, COPY_NIB, ring16_allowed);
-		};
-		const int wide = 1 << 30;
-		for (int z = 0; z < 2; ++z) {
-			if (rerun(to_generic[z], z, 0, grid0)) return -1;
-			if (rerun(to_generic32[z], z, 0, grid0, false, GEOM_CHOOSE, COPY_2BIT, false)) return -1;
-			if (rerun(to_band_wide[z], z, 2, wide, true)) return -1;
-			if (rerun(to_band_span[z], z, 2, wide, false, GEOM_SPAN)) return -1;
-			if (rerun(to_band_bytes[z], z, 2, wide, false, GEOM_CHOOSE, COPY_BYTES)) return -1;
-			if (rerun(same_fewer[0][z], z, 0, std::max(1, std::min<int>(tb_slots, (int)same_fewer[0][z].size())))) return -1;
-			bool all_span = !same_fewer[2][z].empty();
-			for (int32_t i : same_fewer[2][z]) all_span = all_span && b->h_class[i] == CLS_SPAN;
-			if (rerun(same_fewer[2][z], z, 2, std::max(1, std::min<int>(tb_slots, (int)same_fewer[2][z].size())), false, all_span ? GEOM_SPAN : GEOM_CHOOSE)) return -1;
-		}
-		if (fetch()) return -1;
+	for (int round = 0; round < 16; ++round) {
+		RetryLists L;
+		R.tb_slots = tb_slots, R.coop_tb_mult = g->coop_tb_mult;
+		if (const int rc = route_unfinished(g, b, R, round, coop_warned, L)) return rc;
+		if (L.n == 0) break;
+		b->n_retries += (int32_t)L.n;
+		if (L.grow_coop) g->coop_tb_mult *= 2;
+		if (L.fewer) tb_slots = std::max(1, tb_slots / 8);
+		if (run_routes(g, b, L, grid0, tb_slots)) return -1;
+		if (fetch_results(g, b)) return -1;
 	}
 	// nothing may be handed out as a result that is not one
 	for (size_t i = 0; i < n; ++i)
