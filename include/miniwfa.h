@@ -341,6 +341,60 @@ void mwf_wfa_ends(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_
 void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n, const int32_t *tl, const char *const *ts,
                         const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range);
 
+/* ---- Extension alignment: the best-scoring prefix, with a drop-off stop (kernel: csrc/mwf_ends.hip, its EXT form) ---- */
+
+/* Outside a mapper's outermost anchors an alignment is extended from the anchor outwards and stops where it stops being worth it.  The ends-free
+ * allowances {0, INT32_MAX, 0, INT32_MAX} run until one sequence is used up — penalties alone never reward a match — and so force an adapter, a
+ * chimeric tail or a low-quality end into the alignment.  An extension alignment scores every cell of that same pass and answers the best one.
+ *
+ * Parameters, one set per batch: match = A >= 1; zdrop = Z >= 0, or -1 for "no drop rule".
+ *
+ * The pass is the ends-free pass (mwf_ends_t above) with the allowances fixed at {0, INT32_MAX, 0, INT32_MAX}: a single origin cell on diagonal 0, the
+ * same conventions (column = diagonal + tl + 1, an H value k is the last target base consumed, i = d + k), the same band bookkeeping, n_iter and
+ * max_s / max_iter stop rules.  An H cell that is tested after its extension at penalty s has consumed a = (i+1) + (k+1) = d + 2k + 2 bases of the
+ * two sequences together (the origin cell at penalty 0 is a candidate even when it consumes nothing), and its score is
+ *     V = A * a - 2 * s,
+ * twice the score of the cell's alignment under the scheme: match +A, mismatch -(x - A), a gap of L bases -(o + L * (e - A/2)).  A = 1 with the
+ * default penalties (x 4, o1 4, e1 2, o2 15, e2 1) is therefore a 1 / -3 / -4 / -1.5 scheme (second piece -15 / -0.5).  A >= 2 * min(e1, e2)
+ * rewards gaps: legal, but pointless.
+ *
+ * Per penalty s that has at least one such cell:
+ *   1. a_s = the largest a among them (s is constant within a penalty, so the penalty's best V is A * a_s - 2 s); among equal a the lowest column wins.
+ *   2. If A * a_s - 2 s is strictly greater than the best so far, B, it becomes B and its cell (penalty, column, offset, start state) the answer so
+ *      far.  An equal V at a later penalty does not replace it.
+ *   3. F = max(F, a_s): the furthest anti-diagonal any penalty so far has reached.  A * F - 2 s bounds the V of every cell at penalty s from above,
+ *      and falls by 2 per penalty while the frontier stands still.
+ *   4. The pass ends, tested after steps 1-3 of the same penalty, on
+ *        end  (MWF_EXT_END):  some tested cell has i == ql-1 or k == tl-1 (the ends-free end rule with unbounded end allowances), or
+ *        drop (MWF_EXT_DROP): Z >= 0 and B - (A * F - 2 s) > Z;  a penalty at which both hold reports end.
+ *      The max_s / max_iter rules come first, as in every pass: such a pair is stopped (s == -1, ranges and info all -1).
+ * Penalties with no in-matrix H cell leave B and F alone; the drop test still runs for them.  (Under two-piece penalties many penalties are
+ * unreachable or hold only laggard cells: that is why the drop is measured against the monotone F and not against the penalty's own maximum.)
+ *
+ * The result is the remembered cell: s its penalty; te = k+1, qe = i+1, tb = qb = 0 (the ranges are complete in score-only mode too); the CIGAR is
+ * the ends-free traceback started at that cell, in the state of its low three traceback bits if the extension did not move it, else 0; n_iter counts
+ * the whole pass up to the stop.  An empty alignment is legal: te = qe = 0, n_cigar = 0, V = 0.  Per pair info[4] = {V, s_stop, why, F}: s_stop the
+ * penalty at which the pass ended.  Extending to the left of an anchor is extending the two reversed sequences: the caller reverses them. */
+typedef struct { int32_t match, zdrop; } mwf_ext_t; /* 8 bytes */
+#define MWF_EXT_END  0
+#define MWF_EXT_DROP 1
+
+/* mwf_gpu_batch_align_ends under the extension rule.  Refuses (-2, mwf_gpu_last_error) what that call refuses and also match < 1, zdrop < -1 and a pair
+ * with match * (tl+ql+2) >= 2^31 or tl+ql+2 >= 2^30.  Afterwards the batch behaves as after an ends-free align: mwf_gpu_batch_ranges, results, CIGARs,
+ * mwf_gpu_batch_summarize and mwf_gpu_batch_text (of the sub-ranges t[0, te) / q[0, qe)) work, mwf_gpu_batch_map fails, kernel_kind is 3; a traceback arena
+ * that was too small is met by the same re-run, under the same rule.  A later mwf_gpu_batch_align or mwf_gpu_batch_align_ends on the same batch behaves as
+ * if this call had never been made. */
+int mwf_gpu_batch_align_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ext_t *ext);
+/* info of the last extension align, copied to info[n * 4]; waits for the stream.  Fails (negative) when the batch's last align was not an extension. */
+int mwf_gpu_batch_ext_info(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *info);
+/* ... and the device array it lies in (n x 4 int32; complete once the batch is finalised); NULL after any other align. */
+const int32_t *mwf_gpu_batch_dev_ext_info(const mwf_gpu_batch_t *b);
+
+/* The host-buffer calls, as mwf_wfa_ends / mwf_wfa_ends_batch: range[4] and info[4] (one pair) / range[n * 4] and info[n * 4] may be NULL. */
+void mwf_wfa_ext(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range, int32_t *info);
+void mwf_wfa_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t n, const int32_t *tl, const char *const *ts,
+                       const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info);
+
 /* Timing and counters of the most recent mwf_gpu_batch_align on this engine. */
 typedef struct {
 	double  kernel_ms;     /* HIP-event time around the alignment kernels on the engine's stream */

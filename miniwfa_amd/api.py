@@ -47,6 +47,14 @@ class MwfEnds(C.Structure):
 ENDS_FREE = 0x7fffffff  # an allowance that covers any sequence
 
 
+class MwfExt(C.Structure):
+    """mwf_ext_t (include/miniwfa.h), 8 bytes: the match score A of an extension alignment and its drop Z (-1: no drop rule)."""
+    _fields_ = [("match", C.c_int32), ("zdrop", C.c_int32)]
+
+
+MWF_EXT_END, MWF_EXT_DROP = 0, 1  # info[2] of an extension: why its pass ended
+
+
 class GpuStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("cells", C.c_int64), ("cells_pass1", C.c_int64), ("n_launches", C.c_int32),
                 ("n_retries", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("kernel_kind", C.c_int32),
@@ -89,6 +97,7 @@ ABI_SYMBOLS = (
     "mwf_cigar_text", "mwf_gpu_batch_text", "mwf_gpu_batch_dev_text", "mwf_gpu_batch_text_fetch",
     "mwf_alphabet_class", "mwf_alphabet_class16", "mwf_gpu_batch_alphabet",
     "mwf_gpu_batch_align_ends", "mwf_gpu_batch_ranges", "mwf_gpu_batch_dev_ranges", "mwf_wfa_ends", "mwf_wfa_ends_batch",
+    "mwf_gpu_batch_align_ext", "mwf_gpu_batch_ext_info", "mwf_gpu_batch_dev_ext_info", "mwf_wfa_ext", "mwf_wfa_ext_batch",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -208,6 +217,16 @@ def lib() -> C.CDLL:
     L.mwf_wfa_ends.restype = None
     L.mwf_wfa_ends_batch.argtypes = [C.c_void_p, P(MwfOpt), P(MwfEnds), C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p]
     L.mwf_wfa_ends_batch.restype = None
+    L.mwf_gpu_batch_align_ext.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), P(MwfExt)]
+    L.mwf_gpu_batch_align_ext.restype = C.c_int
+    L.mwf_gpu_batch_ext_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mwf_gpu_batch_ext_info.restype = C.c_int
+    L.mwf_gpu_batch_dev_ext_info.argtypes = [C.c_void_p]
+    L.mwf_gpu_batch_dev_ext_info.restype = C.c_void_p
+    L.mwf_wfa_ext.argtypes = [C.c_void_p, P(MwfOpt), P(MwfExt), C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, P(MwfRst), C.c_void_p, C.c_void_p]
+    L.mwf_wfa_ext.restype = None
+    L.mwf_wfa_ext_batch.argtypes = [C.c_void_p, P(MwfOpt), P(MwfExt), C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p, C.c_void_p]
+    L.mwf_wfa_ext_batch.restype = None
     L.mwf_gpu_test_alpha_ms.argtypes = [C.c_void_p, P(C.c_double)]
     L.mwf_gpu_test_alpha_ms.restype = C.c_int
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
@@ -374,6 +393,33 @@ def wfa_ends(t: bytes, q: bytes, opt: MwfOpt, t_beg: int = 0, t_end: int = 0, q_
     return _take(r, km) + (tuple(int(v) for v in rng),)
 
 
+def wfa_ext_batch(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, match: int = 1, zdrop: int = -1, km=None):
+    """mwf_wfa_ext_batch: extension alignment of host buffers -> list of (s, n_iter, cigar, (tb, te, qb, qe), (V, s_stop, why, F))."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    ext = MwfExt(match, zdrop)
+    tl = (C.c_int32 * n)(*[len(t) for t, _ in pairs])
+    ql = (C.c_int32 * n)(*[len(q) for _, q in pairs])
+    ts = (C.c_char_p * n)(*[t for t, _ in pairs])
+    qs = (C.c_char_p * n)(*[q for _, q in pairs])
+    r = (MwfRst * n)()
+    rng = np.zeros((n, 4), dtype=np.int32)
+    info = np.zeros((n, 4), dtype=np.int32)
+    lib().mwf_wfa_ext_batch(km, C.byref(opt), C.byref(ext), n, tl, ts, ql, qs, r, rng.ctypes.data, info.ctypes.data)
+    return [_take(r[i], km) + (tuple(int(v) for v in rng[i]), tuple(int(v) for v in info[i])) for i in range(n)]
+
+
+def wfa_ext(t: bytes, q: bytes, opt: MwfOpt, match: int = 1, zdrop: int = -1, km=None):
+    """mwf_wfa_ext: one extension alignment -> (s, n_iter, cigar words or None, (tb, te, qb, qe), (V, s_stop, why, F))."""
+    ext = MwfExt(match, zdrop)
+    r = MwfRst()
+    rng = np.zeros(4, dtype=np.int32)
+    info = np.zeros(4, dtype=np.int32)
+    lib().mwf_wfa_ext(km, C.byref(opt), C.byref(ext), len(t), t, len(q), q, C.byref(r), rng.ctypes.data, info.ctypes.data)
+    return _take(r, km) + (tuple(int(v) for v in rng), tuple(int(v) for v in info))
+
+
 def cigar2score(opt: MwfOpt, cigar: Sequence[int]):
     """mwf_cigar2score (reference mwf-dbg.c:6-22) -> (score, target length, query length)."""
     arr = (C.c_uint32 * max(1, len(cigar)))(*cigar)
@@ -530,6 +576,27 @@ class Batch:
         rc = lib().mwf_gpu_batch_align_ends(self.eng.h, self.h, C.byref(opt), C.byref(ends))
         if rc != 0:
             raise RuntimeError(f"align_ends failed ({rc}): " + self.eng.error())
+
+    def align_ext(self, opt: MwfOpt, match: int = 1, zdrop: int = -1):
+        """Enqueue an extension alignment (mwf_gpu_batch_align_ext): from the origin outwards, the prefix pair that scores best under match +`match`
+        (include/miniwfa.h, mwf_ext_t); the pass stops at an edge of the matrix or, with zdrop >= 0, once the best score leads by more than zdrop.
+        Afterwards as after align_ends(); ext_info() says what the pass found and why it stopped."""
+        ext = MwfExt(match, zdrop)
+        rc = lib().mwf_gpu_batch_align_ext(self.eng.h, self.h, C.byref(opt), C.byref(ext))
+        if rc != 0:
+            raise RuntimeError(f"align_ext failed ({rc}): " + self.eng.error())
+
+    def ext_info(self) -> np.ndarray:
+        """int32[n, 4]: (V, s_stop, why, F) of every pair of the last align_ext(); waits for the stream.  Raises after any other align."""
+        out = np.zeros((max(1, self.n), 4), dtype=np.int32)
+        rc = lib().mwf_gpu_batch_ext_info(self.eng.h, self.h, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"ext_info failed ({rc}): " + self.eng.error())
+        return out[:self.n]
+
+    def dev_ext_info_ptr(self) -> int | None:
+        """Device pointer to the n x 4 int32 info of the last align_ext(); None after any other align."""
+        return lib().mwf_gpu_batch_dev_ext_info(self.h)
 
     def ranges(self) -> np.ndarray:
         """int32[n, 4]: (tb, te, qb, qe) of every pair of the last align_ends(), half-open; waits for the stream.  Raises after a plain align()."""

@@ -1,4 +1,4 @@
-// mwf_ends.hip — ends-free (semi-global) alignment: wfa_ends_kernel<T>.  The contract is include/miniwfa.h (mwf_ends_t): the cheapest
+// mwf_ends.hip — ends-free (semi-global) and extension alignment: wfa_ends_kernel<T, EXT>.  The contract is include/miniwfa.h (mwf_ends_t): the cheapest
 // global alignment of t[tb, te) against q[qb, qe) where up to t_beg / q_beg bases in front of and t_end / q_end bases behind the aligned
 // ranges are free.
 //
@@ -13,6 +13,12 @@
 //     lane that owns that column publishes its offset and start state;
 //   * the traceback starts at that cell and, where it leaves the matrix, clips what the begin allowance covers instead of emitting it.
 // With four zero allowances all three reduce to the global pass: s, n_iter and the CIGAR words are those of the generic kernel.
+//
+// Extension alignment (mwf_ext_t, same header) is the same pass, driver and kernel under a compile-time EXT flag: the allowances are fixed at
+// {0, INT32_MAX, 0, INT32_MAX}; every tested cell also forms a = bases consumed and the penalty's largest a (lowest column among equals) goes
+// through one 64-bit LDS atomicMax per wave into a slot of the penalty's parity set; after the penalty's barrier the best V = A a - 2 s so far (B),
+// the furthest a (F) and the remembered cell are uniform scalars, the drop rule stops the pass beside the end rule, and the traceback starts
+// at the remembered cell.  The non-EXT instantiations hold none of it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mwf_ends.h"
@@ -36,17 +42,54 @@ __device__ __forceinline__ KEnds &ends_args()
 
 constexpr int32_t kNoEnd = 0x7fffffff; // "no end cell yet" in the column minimum (flags[.][2])
 
+// EXT: the penalty's best cell, one slot per penalty (mod 3) beside dev::Shared's flag sets (cleared two penalties ahead, as they are).  A key is
+// (a + 1) << 33 | inverted column << 3 | start state: the largest is the largest a, then the lowest column, and the whole record rides on one
+// atomic (a + 1 and the column are below 2^30: the host refuses tl + ql + 2 >= 2^30); 0 is "no in-matrix cell at this penalty".
+struct ExtShared {
+	unsigned long long key[3];
+};
+constexpr uint32_t kExtColMask = 0x3fffffffu;
+__device__ __forceinline__ unsigned long long ext_key(int32_t a, int32_t c, int32_t pay)
+{
+	return (unsigned long long)(uint32_t)(a + 1) << 33 | (unsigned long long)(~(uint32_t)c & kExtColMask) << 3 | (uint32_t)pay;
+}
+// The largest key of the wave (uniform): six DPP steps — within quads, within rows of 16, then lane 15 of a row into the next row and lane 31 into the
+// upper half — leave it in lane 63.  Both halves of a key move under the same control; a lane the row mask leaves out sees its own key.  (The same
+// reduction by __shfl_xor is twelve ds_bpermute in a chain of six LDS round trips: measured 1.12 ... 1.21 x the ends-free pass where this is
+// 1.08 ... 1.12 x)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long ext_dpp_max(unsigned long long key)
+{
+	const int32_t lo = (int32_t)(uint32_t)key, hi = (int32_t)(uint32_t)(key >> 32);
+	const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+	const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+	const unsigned long long other = (unsigned long long)ohi << 32 | olo;
+	return other > key ? other : key;
+}
+__device__ __forceinline__ unsigned long long ext_wave_max(unsigned long long key)
+{
+	key = ext_dpp_max<0xb1, 0xf>(key);  // quad_perm:[1,0,3,2]
+	key = ext_dpp_max<0x4e, 0xf>(key);  // quad_perm:[2,3,0,1]
+	key = ext_dpp_max<0x124, 0xf>(key); // row_ror:4
+	key = ext_dpp_max<0x128, 0xf>(key); // row_ror:8
+	key = ext_dpp_max<0x142, 0xa>(key); // row_bcast:15 into rows 1 and 3
+	key = ext_dpp_max<0x143, 0xc>(key); // row_bcast:31 into rows 2 and 3
+	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)key, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(key >> 32), 63);
+	return (unsigned long long)hi << 32 | lo;
+}
+
 struct EndsResult {
 	int32_t status;
 	int32_t s;        // final penalty
 	int32_t info;     // start state of the traceback
 	int32_t te, qe;   // the end cell: target and query bases consumed
 	int64_t cells;    // n_iter
+	int32_t ext[4];   // EXT: mwf_ext_t's info = {V, s_stop, why, F}
 };
 
-// One forward pass over a pair.  TB: store traceback bytes.
-template <int T, bool TB>
-__device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
+// One forward pass over a pair.  TB: store traceback bytes.  EXT: the extension rule (xs: its slots; otherwise not used).
+template <int T, bool TB, bool EXT>
+__device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShared *xs)
 {
 	KArgs &A = E.b;
 	Penalty P;
@@ -76,12 +119,50 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
 		R.info = uni(sh.word[1]);
 		R.te = k + 1, R.qe = endc - 1 - tl + k + 1;
 	};
+	// EXT.  A lane's best cell of the penalty (its columns ascend over its trips: a strict > keeps its lowest) ...
+	int32_t run_a = -1, run_c = 0, run_pay = 0;
+	auto ext_cell = [&](int32_t c, int32_t d, int32_t k, int32_t pay) {
+		const int32_t a = d + 2 * k + 2; // (i + 1) + (k + 1)
+		if (a > run_a) run_a = a, run_c = c, run_pay = pay;
+	};
+	// ... goes to the penalty's slot, one atomic per wave that has a cell ...
+	auto ext_publish = [&](int32_t set) {
+		if (__ballot(run_a >= 0) == 0) return;
+		const unsigned long long key = ext_wave_max(run_a >= 0 ? ext_key(run_a, run_c, run_pay) : 0ull);
+		if (lane == 0) atomicMax(&xs->key[set], key);
+		run_a = -1;
+	};
+	// ... and after the penalty's barrier steps 1-3 of the rule run on uniform scalars: B and its cell, F
+	// (B and F fit 32 bits: 0 <= B <= A F <= A (tl + ql), which the host keeps below 2^31; the key of B's cell is decoded once, at the end)
+	const int32_t ext_A = EXT ? E.match : 0, ext_Z = EXT ? E.zdrop : -1;
+	int32_t ext_B = -1, ext_F = 0, ext_why = 0;
+	int32_t best_s = 0;
+	uint32_t best_lo = 0, best_hi = 0;
+	auto ext_take = [&](int32_t set, int32_t s) {
+		const unsigned long long key = xs->key[set];
+		const uint32_t lo32 = (uint32_t)uni((int32_t)(key & 0xffffffffu)), hi32 = (uint32_t)uni((int32_t)(key >> 32));
+		if ((lo32 | hi32) == 0) return;
+		const int32_t a = (int32_t)(hi32 >> 1) - 1;
+		const int64_t V = (int64_t)ext_A * a - 2 * (int64_t)s;
+		if (V > ext_B) ext_B = (int32_t)V, best_s = s, best_lo = lo32, best_hi = hi32;
+		if (a > ext_F) ext_F = a;
+	};
+	// step 4's drop, at penalty s
+	auto ext_drop = [&](int32_t s) { return ext_Z >= 0 && (int64_t)ext_B - (int64_t)ext_A * ext_F + 2 * (int64_t)s > ext_Z; };
+	// the pass ended at penalty s: the answer is the remembered cell
+	auto ext_finish = [&](int32_t s) {
+		const int32_t a = (int32_t)(best_hi >> 1) - 1, c = (int32_t)(~(((best_hi & 1u) << 29) | (best_lo >> 3)) & kExtColMask);
+		const int32_t d = c - 1 - tl, k = (a - d - 2) >> 1;
+		R.s = best_s, R.info = (int32_t)(best_lo & 7u), R.te = k + 1, R.qe = d + k + 1;
+		R.ext[0] = ext_B, R.ext[1] = s, R.ext[2] = ext_why, R.ext[3] = ext_F;
+	};
 
 	// ---- penalty 0: the origin window and its extension; E and F are dead
 	const int32_t lo0 = tl + 1 - min(E.t_beg, tl), hi0 = tl + 1 + min(E.q_beg, ql);
 	if (tid == 0) {
 		for (int32_t j = 0; j < P.nH; ++j) sh.rng_lo[j] = 1, sh.rng_hi[j] = 0;
 		for (int32_t j = 0; j < 3; ++j) sh.flags[j][0] = sh.flags[j][1] = sh.flags[j][3] = 0, sh.flags[j][2] = kNoEnd;
+		if constexpr (EXT) xs->key[0] = xs->key[1] = xs->key[2] = 0;
 		sh.rng_lo[0] = lo0, sh.rng_hi[0] = hi0;
 	}
 	__syncthreads();
@@ -91,13 +172,22 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
 			const int32_t d = c - 1 - tl;
 			const int32_t k = extend_run(M.ts, M.qs, tl, ql, (d < 0 ? -d : 0) - 1, d); // (every origin cell is inside the matrix)
 			end_test(c, d, k, 0, 0);
+			if constexpr (EXT) ext_cell(c, d, k, 0);
 			M.H[c] = k;
 			M.E1[c] = M.F1[c] = M.E2[c] = M.F2[c] = kNegInf;
 		}
 	}
+	if constexpr (EXT) ext_publish(0);
 	__syncthreads();
 	{
 		const int32_t endc = uni(sh.flags[0][2]);
+		if constexpr (EXT) { // the origin cell is the first candidate, and the only one if it already meets an edge
+			ext_take(0, 0);
+			if (endc != kNoEnd) {
+				ext_finish(0);
+				return R;
+			}
+		} else
 		if (endc != kNoEnd) { // an end cell at no cost (identical sequences, an exact substring, an empty alignment the allowances cover)
 			pick_end(endc);
 			return R;
@@ -152,6 +242,7 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
 			// the flag set of the NEXT penalty: its last readers passed the previous barrier, its next writers start after this penalty's
 			const int32_t nn = npar + 1 == 3 ? 0 : npar + 1;
 			sh.flags[nn][0] = sh.flags[nn][1] = sh.flags[nn][3] = 0, sh.flags[nn][2] = kNoEnd;
+			if constexpr (EXT) xs->key[nn] = 0;
 			if (TB) M.row_off[s_new - 1] = tb_used, M.row_lo[s_new - 1] = lo;
 		}
 		cand_c = kNoEnd;
@@ -184,12 +275,15 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
 				int32_t k = v.h;
 				if (in_matrix(d, k, tl, ql)) {
 					k = extend_run(M.ts, M.qs, tl, ql, k, d);
-					end_test(c, d, k, k == v.h ? (int32_t)(v.tb & 7u) : 0, npar); // start state: as at miniwfa.c:405-407
+					const int32_t pay = k == v.h ? (int32_t)(v.tb & 7u) : 0; // start state: as at miniwfa.c:405-407
+					end_test(c, d, k, pay, npar);
+					if constexpr (EXT) ext_cell(c, d, k, pay);
 				}
 				dH[c] = k, dE1[c] = v.e1, dF1[c] = v.f1, dE2[c] = v.e2, dF2[c] = v.f2;
 				if (TB) tbrow[c] = (uint8_t)v.tb;
 			}
 		}
+		if constexpr (EXT) ext_publish(npar);
 		__syncthreads();
 
 		// ---- bookkeeping, identical on every thread
@@ -222,12 +316,20 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh)
 			R.status = ST_STOPPED;
 			break;
 		}
+		if constexpr (EXT) { // steps 1-3, then the two ends of the pass: an edge of the matrix, or the drop against the furthest anti-diagonal
+			ext_take(par, s);
+			if (endc != kNoEnd) break;
+			if (ext_drop(s)) { ext_why = 1; break; }
+		} else
 		if (endc != kNoEnd) {
 			pick_end(endc);
 			break;
 		}
 	}
 	R.s = s, R.cells = cells;
+	if constexpr (EXT) {
+		if (R.status == ST_OK) ext_finish(s);
+	}
 	return R;
 }
 
@@ -328,13 +430,13 @@ __device__ int32_t ends_traceback(KEnds &E, const PairMem &M, uint32_t *scratch,
 }
 
 // One pair: the pass, the traceback on the first wave, the CIGAR into the pool, the per-pair outputs (dev::finish_pair plus the ranges).
-template <int T>
-__device__ void ends_pair(KEnds &E, Shared &sh, int32_t slot, int32_t pair)
+template <int T, bool EXT>
+__device__ void ends_pair(KEnds &E, Shared &sh, ExtShared *xs, int32_t slot, int32_t pair)
 {
 	KArgs &A = E.b;
 	PairMem M;
 	pair_mem(A, slot, pair, M);
-	const EndsResult R = A.want_cigar ? ends_pass<T, true>(E, M, sh) : ends_pass<T, false>(E, M, sh);
+	const EndsResult R = A.want_cigar ? ends_pass<T, true, EXT>(E, M, sh, xs) : ends_pass<T, false, EXT>(E, M, sh, xs);
 	int32_t status = R.status, n_cigar = 0, tb = -1, qb = -1;
 	int64_t cig_off = 0;
 	if (A.want_cigar && status == ST_OK) {
@@ -367,6 +469,11 @@ __device__ void ends_pair(KEnds &E, Shared &sh, int32_t slot, int32_t pair)
 		const bool ok = status == ST_OK, walked = ok && A.want_cigar;
 		int32_t *rng = E.out_range + 4 * (int64_t)pair;
 		rng[0] = ok ? tb : -1, rng[1] = ok ? R.te : -1, rng[2] = ok ? qb : -1, rng[3] = ok ? R.qe : -1;
+		if constexpr (EXT) {
+			if (!A.want_cigar && ok) rng[0] = rng[2] = 0; // (an extension begins at the origin: known without the walk)
+			int32_t *info = E.out_info + 4 * (int64_t)pair;
+			for (int32_t j = 0; j < 4; ++j) info[j] = ok ? R.ext[j] : -1;
+		}
 		E.sub_t_off[pair] = A.t_off[pair] + (walked ? tb : 0), E.sub_tl[pair] = walked ? R.te - tb : 0;
 		E.sub_q_off[pair] = A.q_off[pair] + (walked ? qb : 0), E.sub_ql[pair] = walked ? R.qe - qb : 0;
 	}
@@ -374,10 +481,15 @@ __device__ void ends_pair(KEnds &E, Shared &sh, int32_t slot, int32_t pair)
 }
 
 // Persistent workgroups: each pulls pairs from a shared counter until the batch is drained.
-template <int T>
+template <int T, bool EXT>
 __global__ __launch_bounds__(T, 1) void wfa_ends_kernel(const EndsArgs)
 {
 	__shared__ Shared sh;
+	ExtShared *xs = nullptr;
+	if constexpr (EXT) {
+		__shared__ ExtShared ext_slots; // (the kernel's own: dev::Shared is the generic kernel's too)
+		xs = &ext_slots;
+	}
 	KEnds &E0 = ends_args();
 	for (;;) {
 		KEnds &E = fresh(E0);
@@ -387,28 +499,32 @@ __global__ __launch_bounds__(T, 1) void wfa_ends_kernel(const EndsArgs)
 		__syncthreads();
 		if (item >= E.b.n_pairs) break;
 		const int32_t pair = E.b.order ? E.b.order[item] : item;
-		ends_pair<T>(E, sh, (int32_t)blockIdx.x, pair);
+		ends_pair<T, EXT>(E, sh, xs, (int32_t)blockIdx.x, pair);
 	}
 }
 
 typedef void (*EndsKernel)(const EndsArgs);
-EndsKernel ends_form(int block) { return block == 256 ? &wfa_ends_kernel<256> : block == 512 ? &wfa_ends_kernel<512> : nullptr; }
+EndsKernel ends_form(int block, bool ext)
+{
+	if (ext) return block == 256 ? &wfa_ends_kernel<256, true> : block == 512 ? &wfa_ends_kernel<512, true> : nullptr;
+	return block == 256 ? &wfa_ends_kernel<256, false> : block == 512 ? &wfa_ends_kernel<512, false> : nullptr;
+}
 
 } // namespace
 
 int launch_ends(const EndsArgs &a, int grid, int block, void *stream)
 {
 	if (a.b.pen.nH > kMaxRing) return -1; // (the window table of dev::Shared; the host refuses such penalty sets)
-	const EndsKernel kernel = ends_form(block);
+	const EndsKernel kernel = ends_form(block, a.ext != 0);
 	if (!kernel) return -1;
-	if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] ends-free launch: T %d, %d pairs, grid %d, allowances %d %d %d %d\n", block, (int)a.b.n_pairs, grid, a.t_beg, a.t_end, a.q_beg, a.q_end);
+	if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] %s launch: T %d, %d pairs, grid %d, allowances %d %d %d %d, match %d, zdrop %d\n", a.ext ? "extension" : "ends-free", block, (int)a.b.n_pairs, grid, a.t_beg, a.t_end, a.q_beg, a.q_end, a.match, a.zdrop);
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, a);
 	return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int ends_kernel_occupancy(int block)
+int ends_kernel_occupancy(int block, bool ext)
 {
-	const EndsKernel kernel = ends_form(block);
+	const EndsKernel kernel = ends_form(block, ext);
 	int n = 0;
 	if (!kernel || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0) != hipSuccess) return 0;
 	return n;

@@ -226,6 +226,19 @@ int mwf_gpu_batch_ranges(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *range)
 	return download(g, range, b->d_range, (size_t)b->n * 16);
 }
 
+/* info {V, s_stop, why, F} of an extension align (mwf_gpu_batch_align_ext) */
+const int32_t *mwf_gpu_batch_dev_ext_info(const mwf_gpu_batch_t *b) { return b && b->ext_last ? b->d_ext_info : nullptr; }
+
+int mwf_gpu_batch_ext_info(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t *info)
+{
+	if (!g || !b || !info) return -1;
+	(void)hipSetDevice(g->device);
+	if (!b->ext_last) { g->err = "mwf_gpu_batch_ext_info: the batch's last align was not an extension (mwf_gpu_batch_align_ext)"; return -2; }
+	if (int rc = finalize(g, b)) return rc;
+	if (b->n == 0) return 0;
+	return download(g, info, b->d_ext_info, (size_t)b->n * 16);
+}
+
 int32_t mwf_gpu_batch_cigar(mwf_gpu_t *g, mwf_gpu_batch_t *b, int32_t i, uint32_t *dst, int32_t cap)
 {
 	if (!g || !b || i < 0 || i >= b->n) return -1;
@@ -696,25 +709,27 @@ void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, i
 	mwf_wfa_batch_multi(km, opt, 1, &tl, &ts, &ql, &qs, r, 1, &dev);
 }
 
-// Ends-free alignment of host buffers (include/miniwfa.h, mwf_ends_t) on a pooled engine of the default device, as run_share does a plain one
-void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n, const int32_t *tl, const char *const *ts,
-                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range)
+// Ends-free alignment of host buffers (include/miniwfa.h, mwf_ends_t) on a pooled engine of the default device, as run_share does a plain one;
+// with `ext` an extension alignment (mwf_ext_t: `ends` is then not read, `info` may be filled)
+static void ends_or_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, const mwf_ext_t *ext, int32_t n, const int32_t *tl, const char *const *ts,
+                              const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
 {
 	if (n <= 0) return;
 	mwf_gpu_t *g = acquire_engine(default_device());
 	HostResult R;
-	std::vector<int32_t> ids((size_t)n), rng((size_t)n * 4);
+	std::vector<int32_t> ids((size_t)n), rng((size_t)n * 4), inf(ext ? (size_t)n * 4 : 0);
 	std::iota(ids.begin(), ids.end(), 0);
 	mwf_gpu_batch_t *b = batch_from_host(g, n, tl, ts, ql, qs, nullptr, 0, nullptr, nullptr);
 	const bool cigar = (opt->flag & MWF_F_CIGAR) != 0;
 	if (!b) R.err = std::string("batch upload failed: ") + mwf_gpu_last_error(g);
 	else {
 		R.s.resize((size_t)n), R.ncig.resize((size_t)n), R.iter.resize((size_t)n);
-		int rc = mwf_gpu_batch_align_ends(g, b, opt, ends);
+		int rc = ext ? mwf_gpu_batch_align_ext(g, b, opt, ext) : mwf_gpu_batch_align_ends(g, b, opt, ends);
 		rc = rc || mwf_gpu_batch_results(g, b, R.s.data(), R.iter.data(), R.ncig.data());
 		rc = rc || (cigar && fetch_cigars(g, b));
 		rc = rc || mwf_gpu_batch_ranges(g, b, rng.data());
-		if (rc) R.err = std::string("ends-free alignment failed: ") + mwf_gpu_last_error(g);
+		rc = rc || (ext && mwf_gpu_batch_ext_info(g, b, inf.data()));
+		if (rc) R.err = std::string(ext ? "extension alignment failed: " : "ends-free alignment failed: ") + mwf_gpu_last_error(g);
 		else if (cigar) R.cig.swap(b->h_cig), R.cigoff = b->h_cigoff;
 		mwf_gpu_batch_free(b);
 	}
@@ -724,6 +739,24 @@ void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, 
 	quiet.flag &= ~MWF_F_DEBUG; // (the traceback end state that flag prints is not kept for ends-free alignments)
 	fill_results(km, &quiet, ids, R, r);
 	if (range) memcpy(range, rng.data(), (size_t)n * 16);
+	if (ext && info) memcpy(info, inf.data(), (size_t)n * 16);
+}
+
+void mwf_wfa_ends_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n, const int32_t *tl, const char *const *ts,
+                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range)
+{
+	ends_or_ext_batch(km, opt, ends, nullptr, n, tl, ts, ql, qs, r, range, nullptr);
+}
+
+void mwf_wfa_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t n, const int32_t *tl, const char *const *ts,
+                       const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
+{
+	ends_or_ext_batch(km, opt, nullptr, ext, n, tl, ts, ql, qs, r, range, info);
+}
+
+void mwf_wfa_ext(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
+{
+	mwf_wfa_ext_batch(km, opt, ext, 1, &tl, &ts, &ql, &qs, r, range, info);
 }
 
 void mwf_wfa_ends(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range)

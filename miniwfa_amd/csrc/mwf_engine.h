@@ -51,16 +51,17 @@ constexpr int kMaxDevices = 64;
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // What distinguishes two kernel variants for the occupancy query (cached_occupancy, mwf_plan.cpp).  kind 2: the band family, 0: the generic kernel, 3: the ends-free
-// kernel (mwf_ends.hip: its block alone); the fields of the other family stay zero.
+// kernel (mwf_ends.hip: its block and whether it is the extension form); the fields of the other family stay zero.
 struct OccKey {
 	int kind = 0, block = 0;
+	bool ext = false;
 	// band family
 	int packed = 0, lane = 0, slots512 = 0, e1 = 0, e2 = 0, lds_bytes = 0; // slots512: span / 2048 of the 512-thread geometry (its chunk slots per wave: 3 ... 6), else 0
 	bool cigar = false, seq2 = false, tab = false, nib = false;
 	// generic kernel
 	bool stream_pass = false, ring16 = false, big_ring = false;
 	int lds_e2_cols = 0;
-	auto tied() const { return std::tie(kind, block, packed, lane, slots512, e1, e2, lds_bytes, cigar, seq2, tab, nib, stream_pass, ring16, big_ring, lds_e2_cols); }
+	auto tied() const { return std::tie(kind, block, ext, packed, lane, slots512, e1, e2, lds_bytes, cigar, seq2, tab, nib, stream_pass, ring16, big_ring, lds_e2_cols); }
 	bool operator<(const OccKey &o) const { return tied() < o.tied(); }
 };
 
@@ -248,11 +249,13 @@ struct mwf_gpu_batch_s {
 	int64_t text_total[MWF_TXT_KINDS] = {0, 0, 0, 0, 0, 0}; // bytes of text in the pool
 	int64_t ops_max_len = -1;          // longest pair (tl + ql): what the workgroup size of those kernels is chosen by (-1: not computed yet)
 	// ends-free alignment (mwf_gpu_batch_align_ends; kernel: mwf_ends.hip).  One allocation, made by the first such align and freed with the batch:
-	// [range: n x 4 int32 | sub_t_off, sub_q_off: n int64 each | sub_tl, sub_ql: n int32 each | order: n int32, longest pair first]
-	bool ends_last = false;            // the batch's last align was ends-free: h_kind is 3 for every pair, ranges exist, maps do not
+	// [range: n x 4 int32 | info: n x 4 int32 | sub_t_off, sub_q_off: n int64 each | sub_tl, sub_ql: n int32 each | order: n int32, longest pair first]
+	bool ends_last = false;            // the batch's last align was ends-free or an extension: h_kind is 3 for every pair, ranges exist, maps do not
+	bool ext_last = false;             // ... an extension (mwf_gpu_batch_align_ext): the kernel's EXT form, info exists
 	mwf_ends_t ends{};                 // its allowances (finalize()'s re-runs use them)
+	mwf_ext_t ext{};                   // ... and, after an extension, its parameters (likewise)
 	DevBuf ends_buf;
-	int32_t *d_range = nullptr, *d_sub_tl = nullptr, *d_sub_ql = nullptr, *d_ends_order = nullptr;
+	int32_t *d_range = nullptr, *d_ext_info = nullptr, *d_sub_tl = nullptr, *d_sub_ql = nullptr, *d_ends_order = nullptr;
 	int64_t *d_sub_t_off = nullptr, *d_sub_q_off = nullptr;
 };
 

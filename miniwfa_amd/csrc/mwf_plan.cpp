@@ -47,6 +47,7 @@ struct Plan {
 	SlotSizes ws;
 	int64_t snap_slot_ints = 0, snap_meta_slot = 0, seg_slot = 0;
 	bool low_mem = false, cigar = false;
+	bool ext = false;          // kind 3: the extension form of the kernel (mwf_ext_t)
 };
 
 typedef mwf_gpu_batch_t::PlanCache::GI GroupInfo;
@@ -220,14 +221,14 @@ void choose_kernel(mwf_gpu_t *g, const LaunchReq &rq, const Penalty &P, Plan &pl
 int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_cols, bool stream_pass, bool ring16)
 {
 	OccKey key;
-	if (pl.kind == 3) key.kind = 3, key.block = pl.block;
+	if (pl.kind == 3) key.kind = 3, key.block = pl.block, key.ext = pl.ext;
 	else if (pl.kind == 2) {
 		key.kind = 2, key.block = pl.band.block, key.packed = pl.band.packed, key.lane = pl.band.lane, key.slots512 = pl.band.block == 512 ? pl.band.span / 2048 : 0;
 		key.e1 = P.e1, key.e2 = P.e2, key.lds_bytes = pl.band.lds_bytes, key.cigar = pl.cigar, key.seq2 = pl.band.seq2 != 0, key.tab = pl.band.tab > 0, key.nib = pl.band.nib != 0;
 	} else key.block = pl.block, key.stream_pass = stream_pass, key.ring16 = ring16, key.big_ring = P.nH > kMaxRing, key.lds_e2_cols = lds_e2_cols;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;
-	const int per = pl.kind == 3 ? ends_kernel_occupancy(pl.block)
+	const int per = pl.kind == 3 ? ends_kernel_occupancy(pl.block, pl.ext)
 	              : pl.kind == 2 && pl.band.lane == 2 ? 1 // (mwf_mid.hip: most of a CU's LDS per workgroup)
 	              : pl.kind == 2 && pl.band.lane ? lane_kernel_occupancy(pl.band.lds_bytes, pl.cigar)
 	              : pl.kind == 2 ? band2_kernel_occupancy(P, pl.band, pl.cigar)
@@ -467,6 +468,7 @@ int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *
 	const Penalty P = make_penalty(opt);
 	Plan pl;
 	pl.kind = 3, pl.cigar = (opt.flag & MWF_F_CIGAR) != 0, pl.block = window_block(rq.group);
+	pl.ext = b->ext_last; // (the form follows the batch, not the request: finalize()'s re-runs repeat the align's mode)
 	const int per_cu = cached_occupancy(g, P, pl, 0, false);
 	const int slots = std::max(1, std::min(rq.slots, g->n_cu * std::max(1, per_cu)));
 	pl.grid = std::max(1, std::min<int>(slots, rq.n_items));
@@ -483,6 +485,7 @@ int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *
 	a.debug_pair = -1, a.out_dbg = nullptr;
 	e.t_beg = b->ends.t_beg, e.t_end = b->ends.t_end, e.q_beg = b->ends.q_beg, e.q_end = b->ends.q_end;
 	e.out_range = b->d_range, e.sub_t_off = b->d_sub_t_off, e.sub_q_off = b->d_sub_q_off, e.sub_tl = b->d_sub_tl, e.sub_ql = b->d_sub_ql;
+	e.ext = pl.ext, e.match = b->ext.match, e.zdrop = b->ext.zdrop, e.out_info = b->d_ext_info;
 	if (ran_kind) *ran_kind = 3;
 	return launch_gated(g, b, rq, pl, 0, "kernel launch failed (ends-free)", [&] { return launch_ends(e, pl.grid, pl.block, g->stream); });
 }
@@ -1049,7 +1052,7 @@ static int launch_classes(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt
 // what every align call resets: the batch's record of its last align and what was derived from that align's CIGARs, the engine's statistics
 static void begin_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, bool ends_free)
 {
-	b->opt = opt, b->ends_last = ends_free;
+	b->opt = opt, b->ends_last = ends_free, b->ext_last = false; // (mwf_gpu_batch_align_ext sets ext_last after this)
 	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
 	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
 	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
@@ -1104,10 +1107,19 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 
 // Ends-free alignment (include/miniwfa.h, mwf_ends_t): one launch of mwf_ends.hip's kernel over all pairs, longest first.  No size classes, no whole-device
 // route, no sequence copies; the plan cache of the plain align is left alone, so that a later mwf_gpu_batch_align finds what its last one left.
-int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends)
+// ... and extension alignment (mwf_ext_t) with it: the same launch under the EXT form of the kernel, `ext` non-null.
+static int align_ends_or_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends, const mwf_ext_t *ext)
 {
-	if (!g || !b || !opt || !ends) return -1;
 	if (const char *why = validate(*opt)) { g->err = why; return -2; }
+	if (ext) {
+		if (ext->match < 1) { g->err = "extension alignment: match must be >= 1"; return -2; }
+		if (ext->zdrop < -1) { g->err = "extension alignment: zdrop must be >= 0, or -1 for no drop rule"; return -2; }
+		for (int32_t i = 0; i < b->n; ++i) {
+			const int64_t len2 = (int64_t)b->h_tl[i] + b->h_ql[i] + 2;
+			if (len2 >= ((int64_t)1 << 30)) { g->err = "extension alignment: tl+ql+2 must be below 2^30"; return -2; }
+			if (ext->match * len2 >= ((int64_t)1 << 31)) { g->err = "extension alignment: match * (tl+ql+2) must be below 2^31"; return -2; }
+		}
+	}
 	if (ends->t_beg < 0 || ends->t_end < 0 || ends->q_beg < 0 || ends->q_end < 0) { g->err = "ends-free alignment: every allowance (t_beg, t_end, q_beg, q_end) must be >= 0"; return -2; }
 	if ((opt->flag & MWF_F_CIGAR) && opt->step > 0) { g->err = "ends-free alignment has no low-memory mode: MWF_F_CIGAR needs opt.step == 0"; return -2; }
 	const Penalty P0 = make_penalty(*opt);
@@ -1118,13 +1130,15 @@ int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 	if (rq.group.max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
 	begin_align(g, b, *opt, true);
 	b->ends = *ends;
+	if (ext) b->ext_last = true, b->ext = *ext;
 	if (b->n == 0) { b->aligned = b->finalized = true; return 0; }
 	const size_t N = (size_t)b->n;
-	if (!b->ends_buf.p) { // [range | sub_t_off | sub_q_off | sub_tl | sub_ql | order]
+	if (!b->ends_buf.p) { // [range | info | sub_t_off | sub_q_off | sub_tl | sub_ql | order]
 		const size_t r_bytes = align_up(N * 16, 16), o_bytes = N * 8, l_bytes = align_up(N * 4, 16);
-		if (ensure(g, b->ends_buf, r_bytes + 2 * o_bytes + 3 * l_bytes)) return -1;
+		if (ensure(g, b->ends_buf, 2 * r_bytes + 2 * o_bytes + 3 * l_bytes)) return -1;
 		char *base = (char*)b->ends_buf.p;
 		b->d_range = (int32_t*)base, base += r_bytes;
+		b->d_ext_info = (int32_t*)base, base += r_bytes;
 		b->d_sub_t_off = (int64_t*)base, base += o_bytes;
 		b->d_sub_q_off = (int64_t*)base, base += o_bytes;
 		b->d_sub_tl = (int32_t*)base, base += l_bytes;
@@ -1142,6 +1156,20 @@ int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 	std::fill(b->h_kind.begin(), b->h_kind.end(), (int8_t)3);
 	b->aligned = true;
 	return 0;
+}
+
+int mwf_gpu_batch_align_ends(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends)
+{
+	if (!g || !b || !opt || !ends) return -1;
+	return align_ends_or_ext(g, b, opt, ends, nullptr);
+}
+
+// Extension alignment (include/miniwfa.h, mwf_ext_t): the ends-free launch with the allowances of an extension from an anchor, under the score rule.
+int mwf_gpu_batch_align_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ext_t *ext)
+{
+	if (!g || !b || !opt || !ext) return -1;
+	const mwf_ends_t ends = {0, INT32_MAX, 0, INT32_MAX};
+	return align_ends_or_ext(g, b, opt, &ends, ext);
 }
 
 } // extern "C"
