@@ -2,8 +2,11 @@
 
   dp_score      a numpy Gotoh DP (two affine gap pieces, the free-end rules) -> the optimal penalty;
   check_cigar   a CIGAR checker: ops and bases agree, the words consume exactly the ranges, the ranges obey the allowances, the words score s;
-  wfa_ends      a small restatement of the header's pass (origin window, end rule, band bookkeeping) -> s, n_iter and the end cell.  It has no
-                shrink, so it stands for pairs with s < 256 only.
+  sweep         the pass both restatements share, on full-width numpy rows: the slice of every penalty from an origin window on, the band bookkeeping,
+                n_iter, and the reference's stripe shrink (wf_stripe_shrink, miniwfa.c:144-171; oracle/mwf_oracle.c ring_shrink): at every penalty that
+                is a multiple of 256 the band [wf_lo, wf_hi] is cut down to its outermost good columns, a column being good if, in any of the last
+                nH = max(x, o1 + e1, o2 + e2) + 1 slices, any of its H, E1, F1, E2, F2 offsets lies inside the matrix;
+  wfa_ends      a small restatement of the header's pass (origin window, end rule) on that sweep -> s, n_iter and the end cell, at any penalty.
 
 Used by tests/test_ends_cpu.py (which checks the three against each other and against the oracle) and tests/test_ends_gpu.py."""
 from __future__ import annotations
@@ -88,66 +91,110 @@ def check_cigar(mw, opt, t: bytes, q: bytes, words, rng, ends, s: int) -> None:
     assert (sc, ct, cq) == (s, te - tb, qe - qb), ((sc, ct, cq), s, rng)
 
 
-def wfa_ends(t: bytes, q: bytes, pen, ends):
-    """The header's pass, restated on full-width numpy rows (dead outside their windows): -> (s, n_iter, te, qe).  No shrink: s < 256 only."""
+def sweep(t: bytes, q: bytes, pen, lo0: int, hi0: int, trace=None, shrinks=None):
+    """The slices of a pass whose origin window is columns lo0 ... hi0 (column = diagonal + tl + 1), rows dead outside their windows.  Yields, per penalty
+    from 0 on, (s, n_iter, c, d, k): columns, diagonals and offsets of the slice's in-matrix H cells after their extension, columns ascending; the caller
+    ends the pass by not asking for more.  The shrink of penalty s runs after s was yielded, as the reference's runs after its end test.
+    trace, a list, receives (lo, hi) of every new slice in diagonals (what Oracle.band_trace gives); shrinks, a list, receives
+    (s, wf_lo, wf_hi before, wf_lo, wf_hi after) in columns."""
     x, o1, e1, o2, e2 = pen
     tl, ql = len(t), len(q)
-    t_beg, t_end, q_beg, q_end = (min(int(ends[0]), tl), min(int(ends[1]), tl), min(int(ends[2]), ql), min(int(ends[3]), ql))
+    ta, qa = np.frombuffer(t, dtype=np.uint8), np.frombuffer(q, dtype=np.uint8)
     cmax = tl + ql + 1
-    dead = lambda: np.full(cmax + 2, NEG, dtype=np.int64)  # noqa: E731
+    nH = max(x, o1 + e1, o2 + e2) + 1  # the slices a shrink looks at; no older one is read again
+    dead = np.full(cmax + 2, NEG, dtype=np.int64)
+    diag = np.arange(cmax + 2, dtype=np.int64) - 1 - tl
+
+    def in_matrix(d, k):
+        i = d + k
+        return (k >= -1) & (k < tl) & (i >= -1) & (i < ql)
 
     def extend(d, k):
         j, i = k + 1, d + k + 1
-        while j < tl and i < ql and t[j] == q[i]:
-            j, i = j + 1, i + 1
+        live = np.arange(j.size)
+        for _ in range(4):  # most runs end within a few bases: all cells at once
+            jj, ii = j[live], i[live]
+            ok = (jj < tl) & (ii < ql)
+            ok[ok] = ta[jj[ok]] == qa[ii[ok]]
+            live = live[ok]
+            if not live.size:
+                return j - 1
+            j[live] += 1
+            i[live] += 1
+        for n in live:  # the few long ones: block by block
+            jj, ii, step = int(j[n]), int(i[n]), 64
+            while True:
+                m = min(step, tl - jj, ql - ii)
+                if m <= 0:
+                    break
+                ne = np.flatnonzero(ta[jj:jj + m] != qa[ii:ii + m])
+                if ne.size:
+                    jj += int(ne[0])
+                    break
+                jj, ii, step = jj + m, ii + m, step * 4
+            j[n] = jj
         return j - 1
 
-    def in_matrix(d, k):
-        return 0 <= k + 1 <= tl and 0 <= d + k + 1 <= ql
-
-    def is_end(d, k):
-        i = d + k
-        return (i == ql - 1 and tl - 1 - k <= t_end) or (k == tl - 1 and ql - 1 - i <= q_end)
-
-    lo, hi = tl + 1 - t_beg, tl + 1 + q_beg
-    H0 = dead()
-    for c in range(lo, hi + 1):
-        d = c - 1 - tl
-        H0[c] = extend(d, (-d if d < 0 else 0) - 1)
-    for c in range(lo, hi + 1):
-        if is_end(c - 1 - tl, int(H0[c])):
-            return 0, 0, int(H0[c]) + 1, c - 1 - tl + int(H0[c]) + 1
-    Hs, E1s, F1s, E2s, F2s = [H0], [dead()], [dead()], [dead()], [dead()]
-    get = lambda rows, s: rows[s] if s >= 0 else dead()  # noqa: E731
-    wf_lo, wf_hi, n_iter, s = lo, hi, 0, 0
+    c = np.arange(lo0, hi0 + 1, dtype=np.int64)
+    d = diag[c]
+    k = extend(d, np.where(d < 0, -d, 0) - 1)  # (every origin cell is inside the matrix)
+    H0 = dead.copy()
+    H0[c] = k
+    rows = {0: (H0, dead, dead, dead, dead)}  # penalty -> H, E1, F1, E2, F2
+    yield 0, 0, c, d, k
+    get = lambda s, n: rows[s][n] if s in rows else dead  # noqa: E731
+    wf_lo, wf_hi, n_iter, s = lo0, hi0, 0, 0
     while True:
         s += 1
-        assert s < 256, "the restatement has no shrink"
         lo, hi = max(wf_lo - 1, 1), min(wf_hi + 1, cmax)
         n_iter += hi - lo + 1
-        c = np.arange(lo, hi + 1)
-        hx, a, b = get(Hs, s - x), get(Hs, s - o1 - e1), get(Hs, s - o2 - e2)
-        g1e, g1f, g2e, g2f = get(E1s, s - e1), get(F1s, s - e1), get(E2s, s - e2), get(F2s, s - e2)
-        ne1 = np.maximum(a[c - 1], g1e[c - 1])
-        ne2 = np.maximum(b[c - 1], g2e[c - 1])
-        nf1 = np.maximum(a[c + 1], g1f[c + 1]) + 1
-        nf2 = np.maximum(b[c + 1], g2f[c + 1]) + 1
-        nh = np.maximum(hx[c] + 1, np.maximum(np.maximum(ne1, ne2), np.maximum(nf1, nf2)))
+        if trace is not None:
+            trace.append((lo - 1 - tl, hi - 1 - tl))
+        c = np.arange(lo, hi + 1, dtype=np.int64)
+        hx, a, b = get(s - x, 0), get(s - o1 - e1, 0), get(s - o2 - e2, 0)
+        g1e, g1f, g2e, g2f = get(s - e1, 1), get(s - e1, 2), get(s - e2, 3), get(s - e2, 4)
+        ne1 = np.maximum(a[lo - 1:hi], g1e[lo - 1:hi])
+        ne2 = np.maximum(b[lo - 1:hi], g2e[lo - 1:hi])
+        nf1 = np.maximum(a[lo + 1:hi + 2], g1f[lo + 1:hi + 2]) + 1
+        nf2 = np.maximum(b[lo + 1:hi + 2], g2f[lo + 1:hi + 2]) + 1
+        nh = np.maximum(hx[lo:hi + 1] + 1, np.maximum(np.maximum(ne1, ne2), np.maximum(nf1, nf2)))
         if nh[0] >= -1:
             wf_lo = lo
         if nh[-1] >= -1:
             wf_hi = hi
-        end = None
-        for n, col in enumerate(c):
-            d, k = int(col) - 1 - tl, int(nh[n])
-            if in_matrix(d, k):
-                k = extend(d, k)
-                nh[n] = k
-                if end is None and is_end(d, k):
-                    end = (k + 1, d + k + 1)
-        for rows, vals in ((Hs, nh), (E1s, ne1), (F1s, nf1), (E2s, ne2), (F2s, nf2)):
-            r = dead()
+        d = diag[lo:hi + 1]
+        inside = np.flatnonzero(in_matrix(d, nh))
+        if inside.size:
+            nh[inside] = extend(d[inside], nh[inside])
+        new = []
+        for vals in (nh, ne1, nf1, ne2, nf2):
+            r = dead.copy()
             r[lo:hi + 1] = vals
-            rows.append(r)
-        if end is not None:
-            return s, n_iter, end[0], end[1]
+            new.append(r)
+        rows[s] = tuple(new)
+        yield s, n_iter, c[inside], d[inside], nh[inside]
+        if (s & 0xff) == 0:  # the shrink, over the slices of penalties s - nH + 1 ... s
+            good = np.zeros(wf_hi - wf_lo + 1, dtype=bool)
+            for r in rows.values():
+                for v in r:
+                    if v is not dead:
+                        good |= in_matrix(diag[wf_lo:wf_hi + 1], v[wf_lo:wf_hi + 1])
+            at = np.flatnonzero(good)
+            assert at.size, "shrink: no good column in the band"
+            was = (wf_lo, wf_hi)
+            wf_lo, wf_hi = was[0] + int(at[0]), was[0] + int(at[-1])
+            if shrinks is not None:
+                shrinks.append((s,) + was + (wf_lo, wf_hi))
+        rows.pop(s - nH + 1, None)
+
+
+def wfa_ends(t: bytes, q: bytes, pen, ends, trace=None, shrinks=None):
+    """The header's pass, restated: -> (s, n_iter, te, qe).  The first penalty with an end cell is the answer, the lowest column wins.  trace, shrinks: see sweep."""
+    tl, ql = len(t), len(q)
+    t_beg, t_end, q_beg, q_end = (min(int(ends[0]), tl), min(int(ends[1]), tl), min(int(ends[2]), ql), min(int(ends[3]), ql))
+    for s, n_iter, c, d, k in sweep(t, q, pen, tl + 1 - t_beg, tl + 1 + q_beg, trace, shrinks):
+        i = d + k
+        end = ((i == ql - 1) & (tl - 1 - k <= t_end)) | ((k == tl - 1) & (ql - 1 - i <= q_end))
+        if end.any():
+            n = int(end.argmax())
+            return s, n_iter, int(k[n]) + 1, int(i[n]) + 1

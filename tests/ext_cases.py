@@ -1,7 +1,7 @@
 """The shared case list of the extension alignment's tests (tests/test_ext_cpu.py, tests/test_ext_gpu.py) and its restated answers, computed once per process.
 
-A case is a batch of pairs under one (A, Z) and the penalty sets it is run under: both sets of tests/test_ends_gpu.py where the restatement
-(ext_ref.wfa_ext, no shrink) stays in its domain, s_stop < 256; test_ext_cpu.py checks that every listed combination does."""
+A case is a batch of pairs under one (A, Z) and the penalty sets it is run under: both sets of tests/test_ends_gpu.py where the pass ends before the
+first shrink, s_stop < 256; test_ext_cpu.py checks that every listed combination does.  (Beyond it: tests/ends_matrix.py.)"""
 from __future__ import annotations
 
 import collections

@@ -1,6 +1,7 @@
 """Yardsticks for the extension alignment (include/miniwfa.h, mwf_ext_t), independent of the library's kernel:
 
-  wfa_ext          the header's rule restated on numpy rows, built like ends_ref.wfa_ends (no shrink: it asserts s_stop < 256);
+  wfa_ext          the header's rule restated on ends_ref.sweep — the slices of a pass from the origin cell, with the reference's stripe shrink every 256
+                   penalties over the last nH slices — as ends_ref.wfa_ends is: steps 1 - 3 on every penalty's tested cells, then the two ends of the pass;
   dp_best          a full prefix Gotoh matrix D[i][j] from the origin (0, 0): s_end = min of D over the last row and the last column, and the yardstick
                    max{A (i + j) - 2 D[i][j] : D[i][j] <= s_end}, which a pass without the drop rule must return exactly, with s_stop == s_end;
   check_ext_cigar  a checker for an extension's CIGAR and ranges: tb = qb = 0, the words consume t[0, te) / q[0, qe) and cost s.
@@ -12,98 +13,32 @@ import collections
 
 import numpy as np
 
-from ends_ref import NEG
+from ends_ref import sweep
 
 ExtRef = collections.namedtuple("ExtRef", "s n_iter te qe V s_stop why F tie_cols tie_later")
 DP_INF = 1 << 28
 
 
-def wfa_ext(t: bytes, q: bytes, pen, A: int, Z: int) -> ExtRef:
+def wfa_ext(t: bytes, q: bytes, pen, A: int, Z: int, trace=None, shrinks=None) -> ExtRef:
     """The extension pass: -> the remembered cell (s, te, qe), n_iter, info (V, s_stop, why, F), and two counts the case list is chosen by: tie_cols, the
-    columns that held a_s at the answer's penalty, and tie_later, the later penalties whose best V equalled B without replacing it."""
-    x, o1, e1, o2, e2 = pen
+    columns that held a_s at the answer's penalty, and tie_later, the later penalties whose best V equalled B without replacing it.  trace, shrinks: see ends_ref.sweep."""
     tl, ql = len(t), len(q)
-    cmax = tl + ql + 1
-    depth = max(x, o1 + e1, o2 + e2)  # rows older than this are never read again
-    dead = np.full(cmax + 2, NEG, dtype=np.int64)
-
-    def extend(d, k):
-        j, i = k + 1, d + k + 1
-        while j < tl and i < ql and t[j] == q[i]:
-            j, i = j + 1, i + 1
-        return j - 1
-
-    def in_matrix(d, k):
-        return 0 <= k + 1 <= tl and 0 <= d + k + 1 <= ql
-
-    def is_end(d, k):
-        return d + k == ql - 1 or k == tl - 1
-
     best = dict(B=None, s=0, te=0, qe=0, tie_cols=0, tie_later=0)
     F = 0
-
-    def steps_1_to_3(s, cells):  # cells: (column, d, k) of every tested cell of penalty s, columns ascending
-        nonlocal F
-        if not cells:
-            return
-        a_s = max(d + 2 * k + 2 for _, d, k in cells)
-        c, d, k = next(v for v in cells if v[1] + 2 * v[2] + 2 == a_s)  # the lowest column among equals
-        V = A * a_s - 2 * s
-        if best["B"] is None or V > best["B"]:
-            best.update(B=V, s=s, te=k + 1, qe=d + k + 1, tie_cols=sum(1 for v in cells if v[1] + 2 * v[2] + 2 == a_s), tie_later=0)
-        elif V == best["B"]:
-            best["tie_later"] += 1
-        F = max(F, a_s)
-
-    def result(n_iter, s_stop, why):
-        return ExtRef(best["s"], n_iter, best["te"], best["qe"], best["B"], s_stop, why, F, best["tie_cols"], best["tie_later"])
-
-    k0 = extend(0, -1)
-    H0 = dead.copy()
-    H0[tl + 1] = k0
-    steps_1_to_3(0, [(tl + 1, 0, k0)])
-    if is_end(0, k0):
-        return result(0, 0, 0)
-    Hs, E1s, F1s, E2s, F2s = [H0], [dead], [dead], [dead], [dead]
-    get = lambda rows, s: rows[s] if s >= 0 else dead  # noqa: E731
-    wf_lo = wf_hi = tl + 1
-    n_iter, s = 0, 0
-    while True:
-        s += 1
-        assert s < 256, "the restatement has no shrink"
-        lo, hi = max(wf_lo - 1, 1), min(wf_hi + 1, cmax)
-        n_iter += hi - lo + 1
-        c = np.arange(lo, hi + 1)
-        hx, a, b = get(Hs, s - x), get(Hs, s - o1 - e1), get(Hs, s - o2 - e2)
-        g1e, g1f, g2e, g2f = get(E1s, s - e1), get(F1s, s - e1), get(E2s, s - e2), get(F2s, s - e2)
-        ne1 = np.maximum(a[c - 1], g1e[c - 1])
-        ne2 = np.maximum(b[c - 1], g2e[c - 1])
-        nf1 = np.maximum(a[c + 1], g1f[c + 1]) + 1
-        nf2 = np.maximum(b[c + 1], g2f[c + 1]) + 1
-        nh = np.maximum(hx[c] + 1, np.maximum(np.maximum(ne1, ne2), np.maximum(nf1, nf2)))
-        if nh[0] >= -1:
-            wf_lo = lo
-        if nh[-1] >= -1:
-            wf_hi = hi
-        cells, end = [], False
-        for n, col in enumerate(c):
-            d, k = int(col) - 1 - tl, int(nh[n])
-            if in_matrix(d, k):
-                k = extend(d, k)
-                nh[n] = k
-                cells.append((int(col), d, k))
-                end = end or is_end(d, k)
-        for rows, vals in ((Hs, nh), (E1s, ne1), (F1s, nf1), (E2s, ne2), (F2s, nf2)):
-            r = dead.copy()
-            r[lo:hi + 1] = vals
-            rows.append(r)
-            if s - depth - 1 >= 0:
-                rows[s - depth - 1] = None
-        steps_1_to_3(s, cells)
-        if end:
-            return result(n_iter, s, 0)
-        if Z >= 0 and best["B"] - (A * F - 2 * s) > Z:
-            return result(n_iter, s, 1)
+    for s, n_iter, c, d, k in sweep(t, q, pen, tl + 1, tl + 1, trace, shrinks):  # c, d, k: every tested cell of penalty s, columns ascending
+        if c.size:  # steps 1 - 3
+            a = d + 2 * k + 2
+            n = int(a.argmax())  # the lowest column among equals
+            a_s = int(a[n])
+            V = A * a_s - 2 * s
+            if best["B"] is None or V > best["B"]:
+                best.update(B=V, s=s, te=int(k[n]) + 1, qe=int(d[n] + k[n]) + 1, tie_cols=int((a == a_s).sum()), tie_later=0)
+            elif V == best["B"]:
+                best["tie_later"] += 1
+            F = max(F, a_s)
+        why = 0 if ((d + k == ql - 1) | (k == tl - 1)).any() else 1 if s > 0 and Z >= 0 and best["B"] - (A * F - 2 * s) > Z else None
+        if why is not None:
+            return ExtRef(best["s"], n_iter, best["te"], best["qe"], best["B"], s, why, F, best["tie_cols"], best["tie_later"])
 
 
 def dp_matrix(t: bytes, q: bytes, pen) -> np.ndarray:
@@ -143,6 +78,12 @@ def dp_best(t: bytes, q: bytes, pen, A: int):
     ij = np.add.outer(np.arange(D.shape[0], dtype=np.int64), np.arange(D.shape[1], dtype=np.int64))
     V = np.where(D <= s_end, A * ij - 2 * D.astype(np.int64), -1)
     return int(V.max()), s_end, D
+
+
+def dp_answer(t: bytes, q: bytes, pen, A: int, te: int, qe: int):
+    """dp_best without the matrix: -> (V, s_end, D[qe][te])."""
+    V, s_end, D = dp_best(t, q, pen, A)
+    return V, s_end, int(D[qe][te])
 
 
 def check_ext_cigar(mw, opt, t: bytes, q: bytes, words, rng, s: int) -> None:

@@ -18,6 +18,7 @@ from test_ends_cpu import PENS, rand_pair
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENDS_OBJ = os.path.join(ROOT, "miniwfa_amd", "csrc", "build", "mwf_ends.hip.o")
+ENDS_KERNELS = {(b, e) for b in (256, 512) for e in ("true", "false")}  # wfa_ends_kernel<T, EXT>: what the object must hold (tests/ends_matrix.py has an entry for each)
 NEW_SYMBOLS = ("mwf_gpu_batch_align_ext", "mwf_gpu_batch_ext_info", "mwf_gpu_batch_dev_ext_info", "mwf_wfa_ext", "mwf_wfa_ext_batch")
 
 
@@ -52,7 +53,7 @@ def test_object_holds_the_ext_kernels():
         syms = subprocess.run([tools["llvm-readelf"], "-sW", co], check=True, capture_output=True, text=True).stdout
     dem = subprocess.run([cxxfilt], input=syms, check=True, capture_output=True, text=True).stdout
     got = {(int(m.group(1)), m.group(2)) for ln in dem.splitlines() for m in [re.search(r"\bFUNC\b.*wfa_ends_kernel<(\d+), (true|false)>", ln)] if m}
-    assert got == {(b, e) for b in (256, 512) for e in ("true", "false")}, got
+    assert got == ENDS_KERNELS, got
 
 
 def check_against_dp(t, q, pen, A, r, what):
@@ -62,9 +63,10 @@ def check_against_dp(t, q, pen, A, r, what):
 
 
 def test_every_case_is_in_the_restatements_domain():
+    """Every case of the list ends below penalty 256, before the first shrink (the restatement itself goes on beyond it: tests/test_ends_matrix_cpu.py)."""
     n = 0
     for case, pen in xc.runs():
-        for (t, q), r in zip(case.pairs, xc.want(case, pen)):  # (wfa_ext asserts s_stop < 256 itself)
+        for (t, q), r in zip(case.pairs, xc.want(case, pen)):
             assert 0 <= r.s <= r.s_stop < 256 and r.why in (0, 1) and (case.Z >= 0 or r.why == 0), (case.name, pen)
             assert r.V == case.A * (r.te + r.qe) - 2 * r.s and 0 <= r.V <= case.A * r.F, (case.name, pen)
             n += 1
