@@ -433,6 +433,8 @@ int32_t mwf_gpu_debug_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *op
  *   "band_fold"         1 (default): score-only with o1 == x the packed kernel folds the gap-open row into its E1 / F1 registers (one row load less per chunk); 0: never
  *   "probe_table"       1 (default): the 512-thread packed kernel, default gap extensions, folded form, takes the first probe of its match extension from per-position 8-mer
  *                       tables in LDS (2 bytes per base of target + query) while two workgroups still share a CU; 0: never
+ *   "band_fold2"        1 (default): score-only launches of that table form with e2 == 1, 3 <= o2 and o2 + e2 <= 16 also fold the row the second gap piece opens from into the
+ *                       E2 / F2 registers one penalty ahead (two row loads per chunk instead of three; same s and n_iter); 0: never
  *   "alpha_remap"       0 (default): only pairs of plain A/C/G/T take the 2-bit copies.  1: on the first align of an uploaded batch, and on every align of a wrapped one, every pair
  *                       with at most four distinct bytes (mwf_alphabet_class 1: lower case, RNA, bases coded 0..3) is copied into a per-batch device arena with its bytes mapped onto A/C/G/T
  *                       and planned and aligned as a plain pair — same s, n_iter and CIGAR; summaries and maps keep reading the original bytes.  A wrapped batch's classes follow its current

@@ -44,6 +44,10 @@ int launch_band2(const BatchArgs &a, int grid, const BandGeom &g0, void *stream)
 	BandGeom g = g0;
 	if (g.nib) return launch_band2_nib(a, grid, g, stream); // the 4-bit form (mwf_band2_nib.hip); no other form reads its copies
 	if (g.tab > 0) { // the table form; a geometry it refuses runs the plain form on the same sequence copies
+		if (g.fold2) { // ... with the second gap piece folded where the plan asked for it; what that unit refuses (a CIGAR launch) is the table form's
+			const int rc2 = launch_band2_tab2(a, grid, g, stream);
+			if (rc2 != -1) return rc2;
+		}
 		const int rc = launch_band2_tab(a, grid, g, stream);
 		if (rc != -1) return rc;
 		g.lds_bytes -= g.tab, g.tab = 0;
@@ -57,6 +61,7 @@ int launch_band2(const BatchArgs &a, int grid, const BandGeom &g0, void *stream)
 int band2_kernel_occupancy(const Penalty &p, const BandGeom &g, bool cigar)
 {
 	if (g.nib) return band2_occupancy_nib(p, g, cigar);
+	if (g.tab > 0 && g.fold2 && !cigar) return band2_occupancy_tab2(p, g, cigar);
 	if (g.tab > 0) return band2_occupancy_tab(p, g, cigar); // (0 for a geometry the table form refuses: choose_kernel then keeps the plain form)
 	if (g.packed == 2 && !has_pen_set(MainBiasedSets{}, p.e1, p.e2)) return p.e1 <= 2 ? band2_occupancy_bi1(p, g, cigar) : band2_occupancy_bi2(p, g, cigar);
 	if (p.e1 == 3) return band2_occupancy_e3(p, g, cigar);

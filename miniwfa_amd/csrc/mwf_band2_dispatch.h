@@ -8,6 +8,8 @@
 //   mwf_band2_bi_deep.hip  ... of (3,1), (3,2), (4,1)
 //   mwf_band2_tab.hip      the table form of the first probe (wfa_band2_tab_kernel): (2,1) on 512 x 3 and 512 x 4, folded only
 //   mwf_band2_nib.hip      the 4-bit form (wfa_band2_nib_kernel): (2,1) on 512 x 3, 512 x 4 and the span geometry
+// and an eighth, added behind them:
+//   mwf_band2_tab2.hip     the table form with the second gap piece folded too (wfa_band2_tab2_kernel): (2,1) on 512 x 3 and 512 x 4, folded, score-only
 // (4,2) is not built: its 10 kb batches run on the span geometry (e2 == 2: the worst-case penalty does not fit plain 16-bit offsets), where 24 history registers
 // per slot spill ~100 VGPRs, and gained 1.17 x / 1.13 x over the generic kernel — below what its code is worth.
 //
@@ -53,6 +55,7 @@ using BiSets = PenSets<PenSet<2, 2>, PenSet<1, 1>>;
 using BiDeepSets = PenSets<PenSet<3, 1>, PenSet<3, 2>, PenSet<4, 1>>;
 using TabSets = PenSets<PenSet<2, 1>>;
 using NibSets = PenSets<PenSet<2, 1>>;
+using Tab2Sets = PenSets<PenSet<2, 1>>;
 using NoSets = PenSets<>;
 
 // ---- geometries: a BandGeom names its compile-time geometry (T threads, K chunk slots per wave, BI4 biased offsets) by block, span and packed

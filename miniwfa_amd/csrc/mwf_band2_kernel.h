@@ -1,6 +1,6 @@
 // mwf_band2_kernel.h — the packed band kernel's template: the fast path for batches of pairs whose offsets fit 16 bits (targets below
 // ~32 kb: BASELINE configs[2], read-length batches, chain-mode gap fills).  Seven units include it (through mwf_band2_dispatch.h) and say which
-// instantiations they hold: mwf_band2.hip, mwf_band2_tab.hip, _nib, _e3, _e4, _bi, _bi_deep.  A unit picks the kernel's form by setting MWF_BAND2_FORM first.
+// instantiations they hold: mwf_band2.hip, mwf_band2_tab.hip, _nib, _e3, _e4, _bi, _bi_deep — and an eighth, mwf_band2_tab2.hip, the table form's second fold.  A unit picks the kernel's form by setting MWF_BAND2_FORM first.
 //
 // One workgroup per pair, a wave owns 256-column chunks (four columns per lane, K chunk slots per wave), E/F wavefronts in
 // registers, one barrier per penalty; reference loops miniwfa.c:261-308 and :212-226, driver :397-426.  What makes it fast
@@ -23,7 +23,8 @@
 #include <type_traits>
 #include "mwf_device.h"
 
-// The form of the kernel a unit compiles: 0 plain, 1 table (mwf_band2_tab.hip), 2 four-bit (mwf_band2_nib.hip).  kTabProbe, kNib and the kernel's name follow from it.
+// The form of the kernel a unit compiles: 0 plain, 1 table (mwf_band2_tab.hip), 2 four-bit (mwf_band2_nib.hip), 3 table with the second gap piece folded
+// (mwf_band2_tab2.hip).  kTabProbe, kNib, kFold2Form and the kernel's name follow from it.
 #ifndef MWF_BAND2_FORM
 #define MWF_BAND2_FORM 0
 #endif
@@ -31,6 +32,8 @@
 #define MWF_BAND2_KERNEL wfa_band2_tab_kernel
 #elif MWF_BAND2_FORM == 2
 #define MWF_BAND2_KERNEL wfa_band2_nib_kernel
+#elif MWF_BAND2_FORM == 3
+#define MWF_BAND2_KERNEL wfa_band2_tab2_kernel
 #else
 #define MWF_BAND2_KERNEL wfa_band2_kernel
 #endif
@@ -65,7 +68,13 @@ constexpr int kFoldMaxLag = 8; // largest o1 + e1 the folded form of the packed 
 constexpr int32_t kDeadPair = (int32_t)0x80008000u;
 // The table form (mwf_band2_tab.hip: MWF_BAND2_FORM 1): the first probe of the match extension reads one halfword per sequence and
 // column from a table of 8-mers (build_probe_table) instead of shifting sixteen bases out of two dwords of the 2-bit copy.  The kernel carries a name of its own.
-constexpr bool kTabProbe = MWF_BAND2_FORM == 1;
+constexpr bool kTabProbe = MWF_BAND2_FORM == 1 || MWF_BAND2_FORM == 3;
+// The second fold (mwf_band2_tab2.hip: MWF_BAND2_FORM 3; band2_pass: kFold2): the table form, score-only, e2 == 1, with the row the SECOND gap piece opens from folded
+// into its E2 / F2 registers one penalty ahead, as FOLD does with the first piece's.  Launched for o2 + e2 <= kFold2MaxLag.  The bound is the default penalties' lag
+// (o2 + e2 = 16), and no more: the form's ageing period is a compile-time count that follows from the bound (kAgeOut), and every penalty of slack in it is one more masked
+// run of each chunk a shrink leaves behind, for every pair — the default set is what the form is measured on, and a set with a longer lag keeps the table form.
+constexpr bool kFold2Form = MWF_BAND2_FORM == 3;
+constexpr int kFold2MaxLag = 16;
 // The 4-bit form (mwf_band2_nib.hip: MWF_BAND2_FORM 2): the S2 paths — sequence copy, first probe, match walks — hold FOUR bits per base,
 // eight bases per dword, base j at bits 4*(j & 7) of dword j >> 3, packed from the image bytes of a pair of 5 to 16 distinct bytes ("alpha16": 0x40 | code,
 // mwf_alphabet.hip).  Everything that differs follows from two constants: kSeqSh, log2 of the bits per base, and kSeqDw, log2 of the bases per dword.  The kernel
@@ -353,6 +362,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	constexpr int FULL = TAB ? 8 : S2 ? kSeqPer : 8; // bases the first probe of the match extension looks at (one dword of the copy: sixteen at 2 bits, eight at 4)
 	constexpr bool kChain = TAB;                          // the table form: the rare tests of a chunk are marked as such, an interior chunk without a long run falls through
 	constexpr bool kGeo = TAB && band2_geo_cached(T, K, TB); // ... and the chunk's probe geometry is read from the slot's registers
+	constexpr bool kFold2 = kFold2Form && TAB && FOLD && !TB && E2 == 1; // the second gap piece folded one penalty ahead (below)
+	static_assert(!kFold2Form || kFold2, "the second fold exists on the table form, folded, score-only, e2 == 1");
 	// a test that is rarely true, for the forms that say so; a macro of this function alone (#undef behind it), written in the condition itself: the hint is lowered
 	// before inlining and does not survive a function or lambda boundary
 #define MWF_RARE(x) (kChain ? __builtin_expect((x), 0) != 0 : (x))
@@ -366,7 +377,20 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	// longer makes at the cell itself.  It makes it e1 penalties EARLIER, in the neighbouring column, where both terms are at hand:
 	// E1[s] > H[s-x] there means "the E1 of penalty s+e1 one column on is an extension".  Bits 3 and 4 of a folded byte say that
 	// (PairMem::tb_fwd), and the walk reads them from the cell an extension would come from (traceback_wave: one more byte per gap run).
-	constexpr int kAgeOut = FOLD ? kFoldMaxLag : D;
+	// kFold2 (e2 == 1): the same for the second piece, whose rows lie further apart.  Reference: E2[s][d] = max(H[s-o2-e2][d-1], E2[s-e2][d-1]), F2 likewise from d+1,
+	// plus one.  The row H[s-o2-e2] is the row of lag o2 at penalty s - e2, so after penalty t the slot's E2 / F2 registers (and its edge-table entries) hold
+	// max(E2[t][d], H[t-o2][d]) and max(F2[t][d], H[t-o2][d]), and penalty t + 1 takes them from the neighbouring column with no row of its own: per chunk ONE load of
+	// the row of lag o2, column-aligned (no neighbour word, no shifts), consumed at the fold — the recurrence waits for the row of lag x alone.  The fold stands
+	// behind the first probe of the match extension, not beside the E1 fold: the row of lag o2 is the one that misses L2, and there it has had the chunk's whole front
+	// and the probe's LDS round trip to arrive.  (Beside the E1 fold, in front of put_edge, measured 13.6 against the table form's 11.4 and this placement's 10.8 ms
+	// per step of the headline batch: profiles/band_fold2/, the patch with both placements in profiles/experiments/.)  The slot's edge-table entry is therefore stored
+	// in two halves, the first piece's in front of the probe and the second piece's behind it.
+	// Ageing: a chunk whose last penalty inside the window was t0 computed rows up to H[t0].  H[t0] is folded at penalty t0 + o2, the o2-th masked run (the folds before
+	// it take the rows before it, the folds behind it rows the masked runs themselves stored dead); the E1 fold's last live row goes in at run x < o2.  The folded value
+	// is read at t0 + o2 + e2 from the registers and from the edge table, and D = max(e1, e2) + 1 further runs overwrite all D ages of the table and every register age
+	// with dead values: o2 + D runs.  With o2 + e2 <= kFold2MaxLag that is at most kFold2MaxLag - E2 + D (18 for the default set, which needs exactly that).
+	constexpr int kAgeOut = kFold2 ? kFold2MaxLag - E2 + D : FOLD ? kFoldMaxLag : D;
+	static_assert(!kFold2 || (kAgeOut >= kFoldMaxLag && kAgeOut < 128), "the second fold ages at least as long as the first; two shrinks are 256 penalties apart");
 	constexpr int kAge = (NWK + 2) * 16; // bytes of one age of the edge table
 	static_assert(D >= 2 && D <= 5, "edge-table ages"); // one table per penalty an E/F can be read back from, plus the one being written: epos[] rotates through them
 	const int32_t tl = M.tl, ql = M.ql, cmax = tl + ql + 1;
@@ -378,7 +402,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	// 8 bytes of slack in front (lane 0 of chunk 0 looks one quad to the left; offsets are unsigned: the slack is part of `lane8`)
 	char *const Hb = (char*)M.H;
 	const uint32_t RS = (uint32_t)W << 1; // bytes per row
-	const int32_t min_lag = min(lagx, min(lag1, lag2));
+	const int32_t lag2r = kFold2 ? lag2 - E2 : lag2; // the lag of the row read for the second gap piece: kFold2 reads it e2 penalties early, at the fold
+	const int32_t min_lag = min(lagx, min(lag1, lag2r));
 	const bool relaxed_stores = min_lag >= 3; // rows written now are first loaded two penalties from now: stores may cross the barrier
 	PassResult R;
 	R.status = ST_OK, R.s = 0, R.info = 0, R.n_snap = 0, R.cells = 0;
@@ -444,7 +469,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	int32_t curH = 0, par = 0;
 	const uint32_t ring_bytes = (uint32_t)nH * RS;
 	// rows of the coming penalty and of its three lags, as byte offsets that advance by one row per penalty (penalty 1 first)
-	uint32_t bn = (uint32_t)(1 % nH) * RS, bx = (uint32_t)((nH - lagx + 1) % nH) * RS, b1 = (uint32_t)((nH - lag1 + 1) % nH) * RS, b2 = (uint32_t)((nH - lag2 + 1) % nH) * RS;
+	uint32_t bn = (uint32_t)(1 % nH) * RS, bx = (uint32_t)((nH - lagx + 1) % nH) * RS, b1 = (uint32_t)((nH - lag1 + 1) % nH) * RS, b2 = (uint32_t)((nH - lag2r + 1) % nH) * RS;
 	// The rows of ONE chunk: H at the three lags (one 8-byte load each) and the word next to the chunk for the two gap-open rows.
 	// (Requesting the coming penalty's rows of the wave's first chunk before or straight behind the barrier was measured in rounds 3-5: no gain, -3 % on the
 	// folded form — the row loads are not what the critical wave waits for; the variants are in profiles/experiments/.)
@@ -453,7 +478,7 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 	auto load_rows = [&](Rows &r, const char *rx, const char *r1, const char *r2, uint32_t off) {
 		const uint32_t noff = off + (uint32_t)nd;
 		r.HX = *(const int2*)(rx + off), r.O2 = *(const int2*)(r2 + off);
-		r.N2 = *(const int32_t*)(r2 + noff);
+		if (!kFold2) r.N2 = *(const int32_t*)(r2 + noff); // (kFold2: O2 is the row of lag o2, folded column by column — no neighbour word)
 		if (!FOLD) r.O1 = *(const int2*)(r1 + off), r.N1 = *(const int32_t*)(r1 + noff);
 	};
 	const int64_t iter_limit = A.max_iter > 0 ? A.max_iter : INT64_MAX;
@@ -614,6 +639,13 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			if (k == K - 1 && wave == NW - 1) *(int2*)(lds2 + wE - (NW - 1) * 16) = make_int2(e1b, e2b);  // slot NWK-1 is slot 0's left neighbour
 			if (k == 0 && wave == 0) *(int2*)(lds2 + wF + (NWK + 1) * 16 + 8) = make_int2(f1a, f2a);       // slot 0 is slot NWK-1's right neighbour
 		};
+		// (kFold2: an entry's first-piece halves (h = 0) and second-piece halves (h = 1) stored apart, four bytes each)
+		auto put_edge_half = [&](int k, int h, int32_t eb, int32_t fa) {
+			*(int32_t*)(lds2 + wE + (k * NW + 1) * 16 + 4 * h) = eb;
+			*(int32_t*)(lds2 + wF + (k * NW + 1) * 16 + 8 + 4 * h) = fa;
+			if (k == K - 1 && wave == NW - 1) *(int32_t*)(lds2 + wE - (NW - 1) * 16 + 4 * h) = eb;
+			if (k == 0 && wave == 0) *(int32_t*)(lds2 + wF + (NWK + 1) * 16 + 8 + 4 * h) = fa;
+		};
 		// (not in the widest geometry: what it hands back goes to the generic kernel, several times slower — it would only do so at penalty 1024
 		// and beyond 1.5 x its span, and the bookkeeping costs the headline kernel 21 more spilled SGPRs)
 		// (the span geometry forecasts later: what it hands back goes to the generic kernel, twice as slow — no more)
@@ -701,14 +733,14 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			// ---- recurrence (dev::wf_cell, miniwfa.c:267-278) on pairs of columns
 			const int32_t E1a = e1h[P1][k][0], E1b = e1h[P1][k][1], F1a = f1h[P1][k][0], F1b = f1h[P1][k][1];
 			const int32_t E2a = e2h[P2][k][0], E2b = e2h[P2][k][1], F2a = f2h[P2][k][0], F2b = f2h[P2][k][1];
-			const int32_t o1mA = FOLD ? 0 : left_of_A(O1.y, N1), o2mA = left_of_A(O2.y, N2), g1mA = left_of_A(E1b, xE1), g2mA = left_of_A(E2b, xE2);
-			const int32_t o1pB = FOLD ? 0 : right_of_B(O1.x, N1), o2pB = right_of_B(O2.x, N2), g1pB = right_of_B(F1a, xF1), g2pB = right_of_B(F2a, xF2);
+			const int32_t o1mA = FOLD ? 0 : left_of_A(O1.y, N1), o2mA = kFold2 ? 0 : left_of_A(O2.y, N2), g1mA = left_of_A(E1b, xE1), g2mA = left_of_A(E2b, xE2);
+			const int32_t o1pB = FOLD ? 0 : right_of_B(O1.x, N1), o2pB = kFold2 ? 0 : right_of_B(O2.x, N2), g1pB = right_of_B(F1a, xF1), g2pB = right_of_B(F2a, xF2);
 			const int32_t ONE = 0x00010001;
-			// (FOLD: the E1 / F1 registers already hold the maximum with the row the gap opens from)
-			int32_t ne1A = FOLD ? g1mA : pk_max(o1mA, g1mA), ne2A = pk_max(o2mA, g2mA);
-			int32_t ne1B = FOLD ? E1a : pk_max(O1.x, E1a), ne2B = pk_max(O2.x, E2a);
-			const int32_t pf1A = FOLD ? F1b : pk_max(O1.y, F1b), pf2A = pk_max(O2.y, F2b); // F before its + 1
-			const int32_t pf1B = FOLD ? g1pB : pk_max(o1pB, g1pB), pf2B = pk_max(o2pB, g2pB);
+			// (FOLD: the E1 / F1 registers already hold the maximum with the row the gap opens from; kFold2: the E2 / F2 registers too)
+			int32_t ne1A = FOLD ? g1mA : pk_max(o1mA, g1mA), ne2A = kFold2 ? g2mA : pk_max(o2mA, g2mA);
+			int32_t ne1B = FOLD ? E1a : pk_max(O1.x, E1a), ne2B = kFold2 ? E2a : pk_max(O2.x, E2a);
+			const int32_t pf1A = FOLD ? F1b : pk_max(O1.y, F1b), pf2A = kFold2 ? F2b : pk_max(O2.y, F2b); // F before its + 1
+			const int32_t pf1B = FOLD ? g1pB : pk_max(o1pB, g1pB), pf2B = kFold2 ? g2pB : pk_max(o2pB, g2pB);
 			int32_t nf1A = pk_add(pf1A, ONE), nf2A = pk_add(pf2A, ONE), nf1B = pk_add(pf1B, ONE), nf2B = pk_add(pf2B, ONE);
 			const int32_t mA = pk_add(HX.x, ONE), mB = pk_add(HX.y, ONE);
 			// (kChain: the four partial maxima first, then the two last ones — one VALU instruction between the halves' last maxima, so that neither follows the
@@ -815,8 +847,9 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 					tbw |= (uint32_t)fA | ((uint32_t)fB << 8);
 				}
 			}
+			// (kFold2: the second piece's registers are folded, written and published behind the first probe, below)
 			e1h[P1][k][0] = ne1A, e1h[P1][k][1] = ne1B, f1h[P1][k][0] = nf1A, f1h[P1][k][1] = nf1B;
-			e2h[P2][k][0] = ne2A, e2h[P2][k][1] = ne2B, f2h[P2][k][0] = nf2A, f2h[P2][k][1] = nf2B;
+			if (!kFold2) e2h[P2][k][0] = ne2A, e2h[P2][k][1] = ne2B, f2h[P2][k][0] = nf2A, f2h[P2][k][1] = nf2B;
 #pragma unroll
 			for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -830,7 +863,8 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 					asm volatile("v_swap_b32 %0, %1" : "+v"(f2h[a - 1][k][i]), "+v"(f2h[a][k][i]));
 				}
 			}
-			put_edge(k, ne1B, ne2B, nf1A, nf2A);
+			if (kFold2) put_edge_half(k, 0, ne1B, nf1A); // (the second piece's halves follow behind the probe)
+			else put_edge(k, ne1B, ne2B, nf1A, nf2A);
 
 #if MWF_B2_TIMING == 2
 			if (timed) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc2) : "v"(hA), "v"(hB), "v"(rjA), "v"(dA) : "memory");
@@ -910,6 +944,14 @@ __device__ PassResult band2_pass(const ArgsT &A, const PairMem &M, Shared &sh, c
 			int32_t cA = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[0], (uint32_t)cnt[2])); // saturating
 			int32_t cB = MWF_BC(int32_t, (us2_t)__builtin_amdgcn_cvt_pk_u16((uint32_t)cnt[1], (uint32_t)cnt[3]));
 			if (TAB) cA = MWF_BC(int32_t, (us2_t)(MWF_BC(us2_t, cA) >> 1)), cB = MWF_BC(int32_t, (us2_t)(MWF_BC(us2_t, cB) >> 1)); // bits -> bases; "no difference" (0xffff) stays above FULL
+			if (kFold2) { // the second fold: with the row of lag o2, what the second piece opens from e2 = 1 penalty from now; unmasked like HX (dead outside ITS window).
+				// Masks, good bits and the edge rule saw the values before the fold; the registers and the edge table take the folded ones.  First use of O2.
+				int32_t px = O2.x, py = O2.y;
+				asm volatile("" : "+v"(px), "+v"(py)); // (volatile: stays behind the probe's wait, and the wait for the row with it)
+				ne2A = pk_max(ne2A, px), ne2B = pk_max(ne2B, py), nf2A = pk_max(nf2A, px), nf2B = pk_max(nf2B, py);
+				e2h[P2][k][0] = ne2A, e2h[P2][k][1] = ne2B, f2h[P2][k][0] = nf2A, f2h[P2][k][1] = nf2B;
+				put_edge_half(k, 1, ne2B, nf2A);
+			}
 #if MWF_B2_TIMING == 2
 			if (timed) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tc3) : "v"(cA), "v"(cB) : "memory");
 #endif
@@ -1239,6 +1281,7 @@ void launch_kernel(const BatchArgs &a, int grid, int lds, hipStream_t st)
 		else
 			fprintf(stderr, "[libmwf_hip] band2 launch: T %d K %d E1 %d E2 %d TB %d S2 %d BI4 %d FOLD %d, %d pairs, grid %d\n", T, K, E1, E2, (int)TB, (int)S2, (int)BI4, (int)FOLD, (int)a.n_pairs, grid);
 		if (kTabProbe) fprintf(stderr, "[libmwf_hip] band2 table probe: table %d B, lds %d B\n", (int)a.band_lds_tab, lds);
+		if (kFold2Form) fprintf(stderr, "[libmwf_hip] band2 second fold: wfa_band2_tab2_kernel, row of lag %d folded one penalty ahead (o2 + e2 %d, bound %d)\n", (int)(a.pen.oe2 - a.pen.e2), (int)a.pen.oe2, kFold2MaxLag);
 	}
 	hipLaunchKernelGGL((MWF_BAND2_KERNEL<T, K, E1, E2, TB, S2, BI4, FOLD>), dim3(grid), dim3(T), lds, st, a);
 }
@@ -1274,8 +1317,13 @@ int launch_one(const BatchArgs &a0, int grid, int lds_seq, int lds_tab, bool seq
 	BatchArgs a = a0;
 	a.band_lds_seq = lds_seq, a.band_lds_tab = lds_tab; // (the table is read by the table form alone; every other form is launched with lds_tab 0)
 	const int lds = lds_seq + lds_tail<T, K, E1, E2>();
-	if (a.want_cigar) launch_variant<T, K, E1, E2, true, S2, BI4>(a, grid, lds, st);
-	else launch_variant<T, K, E1, E2, false, S2, BI4>(a, grid, lds, st);
+	if constexpr (kFold2Form) { // score-only kernels alone: a CIGAR launch is the table form's
+		if (a.want_cigar) return -1;
+		launch_variant<T, K, E1, E2, false, S2, BI4>(a, grid, lds, st);
+	} else {
+		if (a.want_cigar) launch_variant<T, K, E1, E2, true, S2, BI4>(a, grid, lds, st);
+		else launch_variant<T, K, E1, E2, false, S2, BI4>(a, grid, lds, st);
+	}
 	return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1285,7 +1333,8 @@ int occ_one(int lds_seq, bool seq2, bool tb)
 	constexpr bool S2 = band2_geo_seq2(T);
 	if (seq2 != S2) return 0;
 	const int lds = lds_seq + lds_tail<T, K, E1, E2>();
-	return tb ? occ_variant<T, K, E1, E2, true, S2, BI4>(lds) : occ_variant<T, K, E1, E2, false, S2, BI4>(lds);
+	if constexpr (kFold2Form) return tb ? 0 : occ_variant<T, K, E1, E2, false, S2, BI4>(lds);
+	else return tb ? occ_variant<T, K, E1, E2, true, S2, BI4>(lds) : occ_variant<T, K, E1, E2, false, S2, BI4>(lds);
 }
 
 } // namespace

@@ -98,6 +98,7 @@ int mwf_gpu_set(mwf_gpu_t *g, const char *name, int64_t value)
 	else if (!strcmp(name, "dev_retry")) g->dev_retry = value != 0;
 	else if (!strcmp(name, "band_fold")) g->band_fold = value != 0;
 	else if (!strcmp(name, "probe_table")) g->probe_table = value != 0;
+	else if (!strcmp(name, "band_fold2")) g->band_fold2 = value != 0;
 	else if (!strcmp(name, "alpha_remap") && (value == 0 || value == 1)) g->alpha_remap = (int)value;
 	else if (!strcmp(name, "alpha16") && (value == 0 || value == 1)) g->alpha16 = (int)value;
 	else if (!strcmp(name, "trim")) { (void)hipSetDevice(g->device); trim(g); }

@@ -57,11 +57,11 @@ struct OccKey {
 	bool ext = false;
 	// band family
 	int packed = 0, lane = 0, slots512 = 0, e1 = 0, e2 = 0, lds_bytes = 0; // slots512: span / 2048 of the 512-thread geometry (its chunk slots per wave: 3 ... 6), else 0
-	bool cigar = false, seq2 = false, tab = false, nib = false;
+	bool cigar = false, seq2 = false, tab = false, nib = false, fold2 = false;
 	// generic kernel
 	bool stream_pass = false, ring16 = false, big_ring = false;
 	int lds_e2_cols = 0;
-	auto tied() const { return std::tie(kind, block, ext, packed, lane, slots512, e1, e2, lds_bytes, cigar, seq2, tab, nib, stream_pass, ring16, big_ring, lds_e2_cols); }
+	auto tied() const { return std::tie(kind, block, ext, packed, lane, slots512, e1, e2, lds_bytes, cigar, seq2, tab, nib, fold2, stream_pass, ring16, big_ring, lds_e2_cols); }
 	bool operator<(const OccKey &o) const { return tied() < o.tied(); }
 };
 
@@ -85,6 +85,7 @@ struct mwf_gpu_s {
 	bool dev_retry = true;      // batches of reads: the pairs the lane kernel hands back are re-run by a follow-up launch from a device-side list, without the host
 	bool band_fold = true;      // packed band kernel: the folded score-only form where the penalties allow it (o1 == x)
 	bool probe_table = true;    // packed band kernel: the table form of the first probe (mwf_band2_tab.hip) where it applies and two workgroups still share a CU (0: never)
+	bool band_fold2 = true;     // packed band kernel, table form, score-only: the second gap piece folded too (mwf_band2_tab2.hip) where band2_tab2_supported holds (0: never)
 	int64_t probe_table_lds = 0; // mwf_gpu_test_hook "probe_table_lds": LDS bytes (table + sequence copies) above which a launch keeps the plain form (0: 74 KB, choose_kernel) — tests of the fall-back
 	bool div_aware = true;      // weigh the size classes' length limits by the batch's estimated divergence (batches built from host memory)
 	int64_t tun_gen = 0;        // bumped by every successful mwf_gpu_set(): a cached plan of an align (PlanCache) is only replayed under the tunables it was made under

@@ -216,6 +216,8 @@ struct BandGeom {
 	                  // 2: the one-workgroup, one-diagonal-per-lane kernel for a few mid-size pairs (mwf_mid.hip): span = columns of its LDS rows
 	int tab;          // packed kernel, table form (mwf_band2_tab.hip): bytes of lds_bytes that hold the probe table (0: the first probe reads the 2-bit copy)
 	int nib;          // packed kernel, 4-bit form (mwf_band2_nib.hip): the sequence copy holds 4 bits per base, packed from the image bytes of pairs of 5 to 16 distinct bytes ("alpha16"); block 512 or 1024
+	int fold2 = 0;    // packed kernel, table form, score-only: 1 = the launch takes the kernels with the second gap piece folded (mwf_band2_tab2.hip), same LDS layout as `tab`
+	                  // (the last member: the planner's positional initialisers, which end at `nib`, keep their meaning and leave it 0)
 };
 // one pair (or a few) across the whole device: mwf_sys.hip (the per-penalty hand-off kernel of rounds 1-2, mwf_coop.hip, was removed in round 5)
 bool coop_supported(const Penalty &p);
@@ -260,6 +262,7 @@ int  launch_band2_bi1(const BatchArgs &a, int grid, const BandGeom &g, void *str
 int  launch_band2_bi2(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  launch_band2_tab(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
 int  launch_band2_nib(const BatchArgs &a, int grid, const BandGeom &g, void *stream);
+int  launch_band2_tab2(const BatchArgs &a, int grid, const BandGeom &g, void *stream); // the table form with the second gap piece folded (mwf_band2_tab2.hip): score-only, BandGeom::fold2
 int  band2_occupancy_e3(const Penalty &p, const BandGeom &g, bool cigar);
 int  band2_occupancy_e4(const Penalty &p, const BandGeom &g, bool cigar);
 int  band2_occupancy_bi1(const Penalty &p, const BandGeom &g, bool cigar);
@@ -268,6 +271,8 @@ int  band2_occupancy_tab(const Penalty &p, const BandGeom &g, bool cigar);
 int  band2_occupancy_nib(const Penalty &p, const BandGeom &g, bool cigar);
 bool band2_nib_supported(const Penalty &p);          // the 4-bit form (mwf_band2_nib.hip, BandGeom::nib) has kernels for these penalties: gap extensions (2,1)
 bool band2_tab_supported(const Penalty &p, bool band_fold); // the table form of the first probe (mwf_band2_tab.hip, BandGeom::tab) has kernels for these penalties
+int  band2_occupancy_tab2(const Penalty &p, const BandGeom &g, bool cigar);
+bool band2_tab2_supported(const Penalty &p);         // ... and its second fold (mwf_band2_tab2.hip, BandGeom::fold2) too: the table form's sets, e2 == 1, 3 <= o2, o2 + e2 <= 16
 bool band2_biased512_supported(const Penalty &p);  // its five / six-slot copies on biased offsets exist for the set: every set band2_supported takes
 int  band2_biased512_chunks();                       // ... and the 512-thread geometry's copy on biased offsets (8 waves x slots per wave)
 int  band2_span_chunks();                            // 256-column chunks its 1024-thread geometry holds (16 waves x slots per wave)

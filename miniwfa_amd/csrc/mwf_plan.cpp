@@ -212,6 +212,8 @@ void choose_kernel(mwf_gpu_t *g, const LaunchReq &rq, const Penalty &P, Plan &pl
 		if (tab + bg.lds_bytes <= budget) {
 			pl.band.tab = (int)tab, pl.band.lds_bytes = (int)(tab + bg.lds_bytes);
 			pl.cigar = (opt.flag & MWF_F_CIGAR) != 0;
+			// ... and score-only, where band2_tab2_supported holds, with the second gap piece folded as well (mwf_band2_tab2.hip; "band_fold2" 0: never): same LDS, same table
+			pl.band.fold2 = (!pl.cigar && g->band_fold2 && band2_tab2_supported(P)) ? 1 : 0;
 			if (cached_occupancy(g, P, pl, 0, false) < 2) pl.band = bg;
 		}
 	}
@@ -224,7 +226,7 @@ int cached_occupancy(mwf_gpu_t *g, const Penalty &P, const Plan &pl, int lds_e2_
 	if (pl.kind == 3) key.kind = 3, key.block = pl.block, key.ext = pl.ext;
 	else if (pl.kind == 2) {
 		key.kind = 2, key.block = pl.band.block, key.packed = pl.band.packed, key.lane = pl.band.lane, key.slots512 = pl.band.block == 512 ? pl.band.span / 2048 : 0;
-		key.e1 = P.e1, key.e2 = P.e2, key.lds_bytes = pl.band.lds_bytes, key.cigar = pl.cigar, key.seq2 = pl.band.seq2 != 0, key.tab = pl.band.tab > 0, key.nib = pl.band.nib != 0;
+		key.e1 = P.e1, key.e2 = P.e2, key.lds_bytes = pl.band.lds_bytes, key.cigar = pl.cigar, key.seq2 = pl.band.seq2 != 0, key.tab = pl.band.tab > 0, key.nib = pl.band.nib != 0, key.fold2 = pl.band.fold2 != 0;
 	} else key.block = pl.block, key.stream_pass = stream_pass, key.ring16 = ring16, key.big_ring = P.nH > kMaxRing, key.lds_e2_cols = lds_e2_cols;
 	auto it = g->occ_cache.find(key);
 	if (it != g->occ_cache.end()) return it->second;
