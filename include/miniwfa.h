@@ -299,7 +299,7 @@ int mwf_gpu_batch_alphabet(mwf_gpu_t *g, mwf_gpu_batch_t *b, int8_t *host_out);
  * aligns to; an ends-free alignment leaves bases at the ends of the sequences unaligned at no cost, up to four allowances.
  *
  * Allowances.  Each is the largest number of bases that may be left unaligned, free of charge, at the begin or the end of the target or the query.
- * Each must be >= 0 and is clamped to that sequence's length; one set applies to every pair of a batch.  The usual sets:
+ * Each must be >= 0 and is clamped to that sequence's length; one set applies to every pair of a batch (one per pair: mwf_gpu_batch_align_ends_pp below).  The usual sets:
  * read in window {INT32_MAX, INT32_MAX, 0, 0}; extension from an anchor {0, INT32_MAX, 0, INT32_MAX}; overlap {0, INT32_MAX, longest overhang, 0} and its mirror
  * (penalties only: with t_end and q_beg — or t_beg and q_end — both unbounded the empty alignment in that corner of the matrix costs nothing and always wins).
  *
@@ -394,6 +394,52 @@ const int32_t *mwf_gpu_batch_dev_ext_info(const mwf_gpu_batch_t *b);
 void mwf_wfa_ext(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range, int32_t *info);
 void mwf_wfa_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t n, const int32_t *tl, const char *const *ts,
                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info);
+
+/* ---- Per-pair allowances and diagonal bands for the two alignments above (same kernels: csrc/mwf_ends.hip) ---- */
+
+/* A mapper has, for every read, a window with its own slack, an overlap with its own overhang, and a seed diagonal the alignment should stay near.
+ *
+ * Per-pair allowances.  ends[i] is pair i's mwf_ends_t, with the meaning and the clamping stated above; n_ends == 1 gives one set to every pair.
+ *
+ * Band.  band[i] = {d_lo, d_hi} is an inclusive range of diagonals, d = query index - target index as everywhere in this header; from a seed at
+ * (t_pos, q_pos) and a bandwidth bw it is {q_pos - t_pos - bw, q_pos - t_pos + bw}.  It is clamped on the device to the diagonals the matrix has,
+ * [-tl, ql]; any int32 values are legal, and d_lo > d_hi admits nothing.  The answer is the cheapest alignment the allowances permit (for an extension:
+ * the best-scoring cell) among alignments whose EVERY cell lies on a diagonal inside the band — H, E1, F1, E2 and F2 alike: a gap moves one diagonal per
+ * base, so a gap may not leave the band either.
+ *
+ * How it is found: the pass stated above with two clamps.  In columns (diagonal + tl + 1) the clamped band is [blo, bhi];
+ *   Origin.  The window of penalty 0 is intersected with [blo, bhi].
+ *   Growth.  Each new slice is lo = max(wf_lo - 1, 1, blo), hi = min(wf_hi + 1, tl+ql+1, bhi).
+ * Everything else applies to the clamped windows as written: the edge rule, the shrink at multiples of 256, n_iter += hi-lo+1, the stop rules, the end
+ * rule, the extension rule with B, F and the drop test, the traceback and its clipping (by the pair's own begin allowances).  With no band, or a band
+ * that covers [-tl, ql], s, n_iter, ranges, info and CIGAR words are bit for bit those of mwf_gpu_batch_align_ends / mwf_gpu_batch_align_ext.
+ *
+ * Feasibility.  With the allowances clamped to the lengths, an alignment begins on a diagonal of [-t_beg, q_beg] and ends on one of
+ * [ql - tl - q_end, ql - tl + t_end].  An alignment inside the band exists iff the clamped band is non-empty and meets both intervals; for an extension
+ * that is d_lo <= 0 <= d_hi.  A pair whose band admits no alignment is an answer, not an error — one read with a bad seed does not fail a batch —: the
+ * kernel tests the rule at the start of the pair and writes the stopped record, s == -1, n_iter == 0, n_cigar == 0, ranges and info all -1.
+ * s == -1 with n_iter == 0 therefore means "nothing inside the band"; a max_s / max_iter stop always has n_iter >= 1.
+ *
+ * Penalty bound.  gap(tl) + gap(ql) — delete the target, insert the query — leaves the band and does not bound a banded alignment (two unrelated
+ * 100-base sequences under the band {0, 0} cost 400 with the default penalties).  Inside any feasible band lies a path of diagonal steps and one gap:
+ * s <= x * min(tl, ql) + max(gap(tl), gap(ql)).  The workspace of a banded launch is sized by that bound. */
+typedef struct { int32_t d_lo, d_hi; } mwf_band_t; /* 8 bytes, inclusive diagonals */
+
+/* mwf_gpu_batch_align_ends with per-pair parameters.  ends: n_ends host entries, n_ends == 1 (one set for all pairs) or n_ends == n; band: n host
+ * entries, or NULL for no band.  Both are copied before the call returns.  Refuses (-2, mwf_gpu_last_error) what mwf_gpu_batch_align_ends refuses and
+ * also n_ends outside {1, n} and a negative allowance of any pair (the message names the first such pair).  Afterwards the batch behaves as after
+ * mwf_gpu_batch_align_ends (ranges, results, CIGARs, summaries and text of the sub-ranges; mwf_gpu_batch_map fails; kernel_kind 3), and a re-run of
+ * pairs whose traceback arena was too small repeats the same per-pair parameters.  A later mwf_gpu_batch_align, _align_ends or _align_ext on the same
+ * batch behaves as if this call had never been made: neither the allowances nor the band stay. */
+int mwf_gpu_batch_align_ends_pp(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n_ends, const mwf_band_t *band);
+/* mwf_gpu_batch_align_ext under a per-pair band (band: n host entries, not NULL): refuses what that call refuses; afterwards as after it. */
+int mwf_gpu_batch_align_ext_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ext_t *ext, const mwf_band_t *band);
+
+/* The host-buffer calls, on pooled engines as mwf_wfa_ends_batch / mwf_wfa_ext_batch: ends[n_ends] and band[n] (or NULL) / band[n] describe the n pairs. */
+void mwf_wfa_ends_pp_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n_ends, const mwf_band_t *band, int32_t n, const int32_t *tl, const char *const *ts,
+                           const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range);
+void mwf_wfa_ext_band_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, const mwf_band_t *band, int32_t n, const int32_t *tl, const char *const *ts,
+                            const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info);
 
 /* Timing and counters of the most recent mwf_gpu_batch_align on this engine. */
 typedef struct {

@@ -55,6 +55,33 @@ class MwfExt(C.Structure):
 MWF_EXT_END, MWF_EXT_DROP = 0, 1  # info[2] of an extension: why its pass ended
 
 
+class MwfBand(C.Structure):
+    """mwf_band_t (include/miniwfa.h), 8 bytes: the inclusive range of diagonals (query index - target index) an alignment must stay on."""
+    _fields_ = [("d_lo", C.c_int32), ("d_hi", C.c_int32)]
+
+
+def _ends_array(ends, n: int) -> np.ndarray:
+    """(4,) or (n, 4) allowances as a C-contiguous int32 array of shape (1, 4) or (n, 4)."""
+    a = np.ascontiguousarray(np.asarray(ends, dtype=np.int64))
+    if a.shape == (4,):
+        a = a.reshape(1, 4)
+    if a.ndim != 2 or a.shape[1] != 4 or a.shape[0] not in (1, n):
+        raise ValueError(f"ends must have shape (4,) or ({n}, 4), not {a.shape}")
+    return np.ascontiguousarray(np.clip(a, -0x80000000, 0x7fffffff).astype(np.int32))
+
+
+def _band_array(band, n: int):
+    """(n, 2) bands as a C-contiguous int32 array, or None."""
+    if band is None:
+        return None
+    a = np.asarray(band, dtype=np.int64)
+    if n == 0 and a.size == 0:
+        a = a.reshape(0, 2)
+    if a.ndim != 2 or a.shape != (n, 2):
+        raise ValueError(f"band must have shape ({n}, 2), not {a.shape}")
+    return np.ascontiguousarray(np.clip(a, -0x80000000, 0x7fffffff).astype(np.int32))
+
+
 class GpuStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("cells", C.c_int64), ("cells_pass1", C.c_int64), ("n_launches", C.c_int32),
                 ("n_retries", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("kernel_kind", C.c_int32),
@@ -98,6 +125,7 @@ ABI_SYMBOLS = (
     "mwf_alphabet_class", "mwf_alphabet_class16", "mwf_gpu_batch_alphabet",
     "mwf_gpu_batch_align_ends", "mwf_gpu_batch_ranges", "mwf_gpu_batch_dev_ranges", "mwf_wfa_ends", "mwf_wfa_ends_batch",
     "mwf_gpu_batch_align_ext", "mwf_gpu_batch_ext_info", "mwf_gpu_batch_dev_ext_info", "mwf_wfa_ext", "mwf_wfa_ext_batch",
+    "mwf_gpu_batch_align_ends_pp", "mwf_gpu_batch_align_ext_band", "mwf_wfa_ends_pp_batch", "mwf_wfa_ext_band_batch",
     "kmalloc", "kcalloc", "krealloc", "krelocate", "kfree", "km_init", "km_init2", "km_destroy", "km_stat", "km_stat_print",
 )
 
@@ -227,6 +255,14 @@ def lib() -> C.CDLL:
     L.mwf_wfa_ext.restype = None
     L.mwf_wfa_ext_batch.argtypes = [C.c_void_p, P(MwfOpt), P(MwfExt), C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p, C.c_void_p]
     L.mwf_wfa_ext_batch.restype = None
+    L.mwf_gpu_batch_align_ends_pp.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), C.c_void_p, C.c_int32, C.c_void_p]
+    L.mwf_gpu_batch_align_ends_pp.restype = C.c_int
+    L.mwf_gpu_batch_align_ext_band.argtypes = [C.c_void_p, C.c_void_p, P(MwfOpt), P(MwfExt), C.c_void_p]
+    L.mwf_gpu_batch_align_ext_band.restype = C.c_int
+    L.mwf_wfa_ends_pp_batch.argtypes = [C.c_void_p, P(MwfOpt), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p]
+    L.mwf_wfa_ends_pp_batch.restype = None
+    L.mwf_wfa_ext_band_batch.argtypes = [C.c_void_p, P(MwfOpt), P(MwfExt), C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(MwfRst), C.c_void_p, C.c_void_p]
+    L.mwf_wfa_ext_band_batch.restype = None
     L.mwf_gpu_test_alpha_ms.argtypes = [C.c_void_p, P(C.c_double)]
     L.mwf_gpu_test_alpha_ms.restype = C.c_int
     for name, res, args in (("kmalloc", C.c_void_p, [C.c_void_p, C.c_size_t]), ("kcalloc", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_size_t]),
@@ -410,6 +446,43 @@ def wfa_ext_batch(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, match: int 
     return [_take(r[i], km) + (tuple(int(v) for v in rng[i]), tuple(int(v) for v in info[i])) for i in range(n)]
 
 
+def wfa_ends_pp_batch(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, ends, band=None, km=None):
+    """mwf_wfa_ends_pp_batch: ends-free alignment of host buffers under per-pair allowances (ends: (4,) or (n, 4)) and bands (band: (n, 2) or None)
+    -> list of (s, n_iter, cigar, (tb, te, qb, qe))."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    e, bd = _ends_array(ends, n), _band_array(band, n)
+    tl = (C.c_int32 * n)(*[len(t) for t, _ in pairs])
+    ql = (C.c_int32 * n)(*[len(q) for _, q in pairs])
+    ts = (C.c_char_p * n)(*[t for t, _ in pairs])
+    qs = (C.c_char_p * n)(*[q for _, q in pairs])
+    r = (MwfRst * n)()
+    rng = np.zeros((n, 4), dtype=np.int32)
+    lib().mwf_wfa_ends_pp_batch(km, C.byref(opt), e.ctypes.data, e.shape[0], None if bd is None else bd.ctypes.data, n, tl, ts, ql, qs, r, rng.ctypes.data)
+    return [_take(r[i], km) + (tuple(int(v) for v in rng[i]),) for i in range(n)]
+
+
+def wfa_ext_band_batch(pairs: Sequence[tuple[bytes, bytes]], opt: MwfOpt, band, match: int = 1, zdrop: int = -1, km=None):
+    """mwf_wfa_ext_band_batch: extension alignment of host buffers under per-pair bands (band: (n, 2))
+    -> list of (s, n_iter, cigar, (tb, te, qb, qe), (V, s_stop, why, F))."""
+    n = len(pairs)
+    if n == 0:
+        return []
+    ext, bd = MwfExt(match, zdrop), _band_array(band, n)
+    if bd is None:
+        raise ValueError("band must not be None")
+    tl = (C.c_int32 * n)(*[len(t) for t, _ in pairs])
+    ql = (C.c_int32 * n)(*[len(q) for _, q in pairs])
+    ts = (C.c_char_p * n)(*[t for t, _ in pairs])
+    qs = (C.c_char_p * n)(*[q for _, q in pairs])
+    r = (MwfRst * n)()
+    rng = np.zeros((n, 4), dtype=np.int32)
+    info = np.zeros((n, 4), dtype=np.int32)
+    lib().mwf_wfa_ext_band_batch(km, C.byref(opt), C.byref(ext), bd.ctypes.data, n, tl, ts, ql, qs, r, rng.ctypes.data, info.ctypes.data)
+    return [_take(r[i], km) + (tuple(int(v) for v in rng[i]), tuple(int(v) for v in info[i])) for i in range(n)]
+
+
 def wfa_ext(t: bytes, q: bytes, opt: MwfOpt, match: int = 1, zdrop: int = -1, km=None):
     """mwf_wfa_ext: one extension alignment -> (s, n_iter, cigar words or None, (tb, te, qb, qe), (V, s_stop, why, F))."""
     ext = MwfExt(match, zdrop)
@@ -577,11 +650,28 @@ class Batch:
         if rc != 0:
             raise RuntimeError(f"align_ends failed ({rc}): " + self.eng.error())
 
-    def align_ext(self, opt: MwfOpt, match: int = 1, zdrop: int = -1):
+    def align_ends_pp(self, opt: MwfOpt, ends, band=None):
+        """Enqueue an ends-free alignment under per-pair parameters (mwf_gpu_batch_align_ends_pp): ends is array-like of shape (4,) — one set of
+        (t_beg, t_end, q_beg, q_end) for every pair — or (n, 4); band is None or array-like of shape (n, 2), the inclusive diagonals (d_lo, d_hi),
+        d = query index - target index, pair i's alignment must stay on (include/miniwfa.h, mwf_band_t).  A pair whose band admits no alignment
+        comes back with s == -1 and n_iter == 0.  Afterwards as after align_ends()."""
+        e, bd = _ends_array(ends, self.n), _band_array(band, self.n)
+        rc = lib().mwf_gpu_batch_align_ends_pp(self.eng.h, self.h, C.byref(opt), e.ctypes.data, e.shape[0], None if bd is None else bd.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"align_ends_pp failed ({rc}): " + self.eng.error())
+
+    def align_ext(self, opt: MwfOpt, match: int = 1, zdrop: int = -1, band=None):
         """Enqueue an extension alignment (mwf_gpu_batch_align_ext): from the origin outwards, the prefix pair that scores best under match +`match`
         (include/miniwfa.h, mwf_ext_t); the pass stops at an edge of the matrix or, with zdrop >= 0, once the best score leads by more than zdrop.
+        band: None, or array-like of shape (n, 2): the diagonals (d_lo, d_hi) pair i's extension must stay on (mwf_gpu_batch_align_ext_band).
         Afterwards as after align_ends(); ext_info() says what the pass found and why it stopped."""
         ext = MwfExt(match, zdrop)
+        bd = _band_array(band, self.n)
+        if bd is not None:
+            rc = lib().mwf_gpu_batch_align_ext_band(self.eng.h, self.h, C.byref(opt), C.byref(ext), bd.ctypes.data)
+            if rc != 0:
+                raise RuntimeError(f"align_ext failed ({rc}): " + self.eng.error())
+            return
         rc = lib().mwf_gpu_batch_align_ext(self.eng.h, self.h, C.byref(opt), C.byref(ext))
         if rc != 0:
             raise RuntimeError(f"align_ext failed ({rc}): " + self.eng.error())

@@ -19,6 +19,9 @@ struct EndsArgs {
 	int32_t ext;               // 0: ends-free, 1: extension
 	int32_t match, zdrop;      // mwf_ext_t: A >= 1; Z >= 0, or -1 for no drop rule
 	int32_t *out_info;         // [pair][4] = {V, s_stop, why, F}; all -1 for a stopped pair
+	// per-pair parameters (mwf_gpu_batch_align_ends_pp / _ext_band), both null for the calls that have one set per batch
+	const int32_t *pp_ends;    // [pair][4] = {t_beg, t_end, q_beg, q_end}, each >= 0: read instead of the four scalars above
+	const int32_t *pp_band;    // [pair][2] = {d_lo, d_hi}, mwf_band_t: the pass stays on these diagonals; null: no band
 };
 
 // launch wrappers implemented in mwf_ends.hip; block: 256 or 512

@@ -19,6 +19,11 @@
 // through one 64-bit LDS atomicMax per wave into a slot of the penalty's parity set; after the penalty's barrier the best V = A a - 2 s so far (B),
 // the furthest a (F) and the remembered cell are uniform scalars, the drop rule stops the pass beside the end rule, and the traceback starts
 // at the remembered cell.  The non-EXT instantiations hold none of it.
+//
+// Per-pair allowances and a per-pair diagonal band (mwf_band_t, same header) are run-time properties of the same four kernels: ends_pair reads the pair's
+// allowances and band (EndsArgs::pp_ends / pp_band; null: the kernarg scalars, no band) into uniform values, applies the feasibility rule — a pair whose band
+// admits no alignment gets the stopped record without a pass — and hands the pass the band as a column range [blo, bhi]; the pass intersects the origin
+// window with it and grows a slice no further than it.  Without a band blo = 1 and bhi = tl + ql + 1, the limits the growth has always had.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mwf_ends.h"
@@ -78,6 +83,12 @@ __device__ __forceinline__ unsigned long long ext_wave_max(unsigned long long ke
 	return (unsigned long long)hi << 32 | lo;
 }
 
+// What a pair's pass and traceback read instead of the kernarg allowances: the pair's own allowances (or the batch's) and its band in columns, all uniform.
+struct PairEnds {
+	int32_t t_beg, t_end, q_beg, q_end;
+	int32_t blo, bhi; // the band, clamped to the matrix: columns blo..bhi (1..cmax when there is none)
+};
+
 struct EndsResult {
 	int32_t status;
 	int32_t s;        // final penalty
@@ -89,7 +100,7 @@ struct EndsResult {
 
 // One forward pass over a pair.  TB: store traceback bytes.  EXT: the extension rule (xs: its slots; otherwise not used).
 template <int T, bool TB, bool EXT>
-__device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShared *xs)
+__device__ EndsResult ends_pass(KEnds &E, const PairEnds &pe, const PairMem &M, Shared &sh, ExtShared *xs)
 {
 	KArgs &A = E.b;
 	Penalty P;
@@ -98,7 +109,8 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShare
 	const int32_t tl = M.tl, ql = M.ql, cmax = tl + ql + 1; // columns 1..cmax hold diagonals -tl..ql
 	const int32_t tid = threadIdx.x, lane = tid & 63, wave0 = tid & ~63;
 	const int64_t W = A.W;
-	const int32_t t_end = E.t_end, q_end = E.q_end;
+	const int32_t t_end = pe.t_end, q_end = pe.q_end;
+	const int32_t blo = pe.blo, bhi = pe.bhi; // 1 <= blo <= bhi <= cmax
 	EndsResult R;
 	R.status = ST_OK, R.s = 0, R.info = 0, R.te = -1, R.qe = -1, R.cells = 0;
 
@@ -157,8 +169,8 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShare
 		R.ext[0] = ext_B, R.ext[1] = s, R.ext[2] = ext_why, R.ext[3] = ext_F;
 	};
 
-	// ---- penalty 0: the origin window and its extension; E and F are dead
-	const int32_t lo0 = tl + 1 - min(E.t_beg, tl), hi0 = tl + 1 + min(E.q_beg, ql);
+	// ---- penalty 0: the origin window, cut to the band (the feasibility rule of ends_pair left it non-empty), and its extension; E and F are dead
+	const int32_t lo0 = max(tl + 1 - min(pe.t_beg, tl), blo), hi0 = min(tl + 1 + min(pe.q_beg, ql), bhi);
 	if (tid == 0) {
 		for (int32_t j = 0; j < P.nH; ++j) sh.rng_lo[j] = 1, sh.rng_hi[j] = 0;
 		for (int32_t j = 0; j < 3; ++j) sh.flags[j][0] = sh.flags[j][1] = sh.flags[j][3] = 0, sh.flags[j][2] = kNoEnd;
@@ -199,9 +211,9 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShare
 	int64_t cells = 0, tb_used = 0;
 
 	for (;;) {
-		// ---- window of the new slice (miniwfa.c:417-418)
-		const int32_t lo = wf_lo > 1 ? wf_lo - 1 : 1;
-		const int32_t hi = wf_hi < cmax ? wf_hi + 1 : cmax;
+		// ---- window of the new slice (miniwfa.c:417-418), held inside the band (blo <= wf_lo and wf_hi <= bhi throughout)
+		const int32_t lo = wf_lo > blo ? wf_lo - 1 : blo;
+		const int32_t hi = wf_hi < bhi ? wf_hi + 1 : bhi;
 		const int32_t w = hi - lo + 1;
 		const int32_t s_new = s + 1;
 		const int32_t newH = curH + 1 == P.nH ? 0 : curH + 1;
@@ -338,7 +350,7 @@ __device__ EndsResult ends_pass(KEnds &E, const PairMem &M, Shared &sh, ExtShare
 // allowance) of them are clipped — that is qb or tb — and the rest is one I or D run, merged with an adjacent run of the same operation.
 // Ops are written backwards from the end of the scratch buffer.  Returns n_cigar (>= 0) or -1 when the buffer is too small or the walk
 // ran out of rows.
-__device__ int32_t ends_traceback(KEnds &E, const PairMem &M, uint32_t *scratch, int64_t cap, const EndsResult &R, int32_t *tb_out, int32_t *qb_out)
+__device__ int32_t ends_traceback(KEnds &E, const PairEnds &pe, const PairMem &M, uint32_t *scratch, int64_t cap, const EndsResult &R, int32_t *tb_out, int32_t *qb_out)
 {
 	KArgs &A = E.b;
 	const auto &P = A.pen;
@@ -416,11 +428,11 @@ __device__ int32_t ends_traceback(KEnds &E, const PairMem &M, uint32_t *scratch,
 	int32_t tb = 0, qb = 0;
 	if (i >= 0) { // query bases in front of the walk: clip what q_beg covers, insert the rest
 		const int32_t L = i + 1;
-		qb = min(L, E.q_beg);
+		qb = min(L, pe.q_beg);
 		if (L > qb) push(1, L - qb);
 	} else if (k >= 0) {
 		const int32_t L = k + 1;
-		tb = min(L, E.t_beg);
+		tb = min(L, pe.t_beg);
 		if (L > tb) push(2, L - tb);
 	}
 	push(-2, 0); // flush the pending run
@@ -436,14 +448,38 @@ __device__ void ends_pair(KEnds &E, Shared &sh, ExtShared *xs, int32_t slot, int
 	KArgs &A = E.b;
 	PairMem M;
 	pair_mem(A, slot, pair, M);
-	const EndsResult R = A.want_cigar ? ends_pass<T, true, EXT>(E, M, sh, xs) : ends_pass<T, false, EXT>(E, M, sh, xs);
+	// the pair's allowances and band: one scalar load each where the launch has per-pair arrays
+	PairEnds pe;
+	pe.t_beg = E.t_beg, pe.t_end = E.t_end, pe.q_beg = E.q_beg, pe.q_end = E.q_end;
+	if (E.pp_ends) {
+		const int32_t *p = E.pp_ends + 4 * (int64_t)pair;
+		pe.t_beg = uni(p[0]), pe.t_end = uni(p[1]), pe.q_beg = uni(p[2]), pe.q_end = uni(p[3]);
+	}
+	const int32_t tl = M.tl, ql = M.ql;
+	pe.blo = 1, pe.bhi = tl + ql + 1;
+	bool feasible = true;
+	if (E.pp_band) {
+		const int32_t *p = E.pp_band + 2 * (int64_t)pair;
+		const int32_t d_lo = uni(p[0]), d_hi = uni(p[1]);
+		// the feasibility rule (mwf_ends_band.h ends_band_feasible, restated): the band clamped to [-tl, ql] is non-empty and meets the origin diagonals
+		// [-min(t_beg, tl), min(q_beg, ql)] and the end diagonals [ql - tl - min(q_end, ql), ql - tl + min(t_end, tl)].  Every term lies in [-tl, ql].
+		feasible = d_lo <= d_hi && d_lo <= ql && d_hi >= -tl;
+		if (feasible) {
+			const int32_t dl = max(d_lo, -tl), dh = min(d_hi, ql);
+			feasible = dl <= min(pe.q_beg, ql) && dh >= -min(pe.t_beg, tl) && dl <= ql - tl + min(pe.t_end, tl) && dh >= ql - tl - min(pe.q_end, ql);
+			pe.blo = dl + tl + 1, pe.bhi = dh + tl + 1;
+		}
+	}
+	EndsResult R;
+	if (feasible) R = A.want_cigar ? ends_pass<T, true, EXT>(E, pe, M, sh, xs) : ends_pass<T, false, EXT>(E, pe, M, sh, xs);
+	else R.status = ST_STOPPED, R.s = 0, R.info = 0, R.te = R.qe = -1, R.cells = 0; // nothing inside the band: the stopped record with n_iter == 0
 	int32_t status = R.status, n_cigar = 0, tb = -1, qb = -1;
 	int64_t cig_off = 0;
 	if (A.want_cigar && status == ST_OK) {
 		__syncthreads();
 		if (threadIdx.x < 64) {
 			uint32_t *scratch = A.cig_scratch + (int64_t)slot * A.cig_scratch_slot;
-			n_cigar = ends_traceback(E, M, scratch, A.cig_scratch_slot, R, &tb, &qb);
+			n_cigar = ends_traceback(E, pe, M, scratch, A.cig_scratch_slot, R, &tb, &qb);
 			if (n_cigar < 0) status = ST_INTERNAL, n_cigar = 0;
 			else {
 				unsigned long long off = 0;
@@ -517,7 +553,7 @@ int launch_ends(const EndsArgs &a, int grid, int block, void *stream)
 	if (a.b.pen.nH > kMaxRing) return -1; // (the window table of dev::Shared; the host refuses such penalty sets)
 	const EndsKernel kernel = ends_form(block, a.ext != 0);
 	if (!kernel) return -1;
-	if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] %s launch: T %d, %d pairs, grid %d, allowances %d %d %d %d, match %d, zdrop %d\n", a.ext ? "extension" : "ends-free", block, (int)a.b.n_pairs, grid, a.t_beg, a.t_end, a.q_beg, a.q_end, a.match, a.zdrop);
+	if (getenv("MWF_DEBUG")) fprintf(stderr, "[libmwf_hip] %s launch: T %d, %d pairs, grid %d, allowances %d %d %d %d, match %d, zdrop %d, per-pair allowances %d, band %d\n", a.ext ? "extension" : "ends-free", block, (int)a.b.n_pairs, grid, a.t_beg, a.t_end, a.q_beg, a.q_end, a.match, a.zdrop, a.pp_ends ? 1 : 0, a.pp_band ? 1 : 0);
 	hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, a);
 	return hipGetLastError() == hipSuccess ? 0 : -2;
 }

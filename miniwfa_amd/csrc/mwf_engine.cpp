@@ -711,9 +711,9 @@ void mwf_wfa_exact(void *km, const mwf_opt_t *opt, int32_t tl, const char *ts, i
 }
 
 // Ends-free alignment of host buffers (include/miniwfa.h, mwf_ends_t) on a pooled engine of the default device, as run_share does a plain one;
-// with `ext` an extension alignment (mwf_ext_t: `ends` is then not read, `info` may be filled)
+// with `ext` an extension alignment (mwf_ext_t: `ends` is then not read, `info` may be filled); with `pp` the per-pair calls (mwf_band_t), which refuse a bad n_ends themselves
 static void ends_or_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, const mwf_ext_t *ext, int32_t n, const int32_t *tl, const char *const *ts,
-                              const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
+                              const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info, bool pp = false, int32_t n_ends = 0, const mwf_band_t *band = nullptr)
 {
 	if (n <= 0) return;
 	mwf_gpu_t *g = acquire_engine(default_device());
@@ -725,7 +725,8 @@ static void ends_or_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *
 	if (!b) R.err = std::string("batch upload failed: ") + mwf_gpu_last_error(g);
 	else {
 		R.s.resize((size_t)n), R.ncig.resize((size_t)n), R.iter.resize((size_t)n);
-		int rc = ext ? mwf_gpu_batch_align_ext(g, b, opt, ext) : mwf_gpu_batch_align_ends(g, b, opt, ends);
+		int rc = ext ? (pp ? mwf_gpu_batch_align_ext_band(g, b, opt, ext, band) : mwf_gpu_batch_align_ext(g, b, opt, ext))
+		             : (pp ? mwf_gpu_batch_align_ends_pp(g, b, opt, ends, n_ends, band) : mwf_gpu_batch_align_ends(g, b, opt, ends));
 		rc = rc || mwf_gpu_batch_results(g, b, R.s.data(), R.iter.data(), R.ncig.data());
 		rc = rc || (cigar && fetch_cigars(g, b));
 		rc = rc || mwf_gpu_batch_ranges(g, b, rng.data());
@@ -753,6 +754,18 @@ void mwf_wfa_ext_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int
                        const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
 {
 	ends_or_ext_batch(km, opt, nullptr, ext, n, tl, ts, ql, qs, r, range, info);
+}
+
+void mwf_wfa_ends_pp_batch(void *km, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n_ends, const mwf_band_t *band, int32_t n, const int32_t *tl, const char *const *ts,
+                           const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range)
+{
+	ends_or_ext_batch(km, opt, ends, nullptr, n, tl, ts, ql, qs, r, range, nullptr, true, n_ends, band);
+}
+
+void mwf_wfa_ext_band_batch(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, const mwf_band_t *band, int32_t n, const int32_t *tl, const char *const *ts,
+                            const int32_t *ql, const char *const *qs, mwf_rst_t *r, int32_t *range, int32_t *info)
+{
+	ends_or_ext_batch(km, opt, nullptr, ext, n, tl, ts, ql, qs, r, range, info, true, 0, band);
 }
 
 void mwf_wfa_ext(void *km, const mwf_opt_t *opt, const mwf_ext_t *ext, int32_t tl, const char *ts, int32_t ql, const char *qs, mwf_rst_t *r, int32_t *range, int32_t *info)

@@ -250,7 +250,7 @@ struct mwf_gpu_batch_s {
 	int64_t text_total[MWF_TXT_KINDS] = {0, 0, 0, 0, 0, 0}; // bytes of text in the pool
 	int64_t ops_max_len = -1;          // longest pair (tl + ql): what the workgroup size of those kernels is chosen by (-1: not computed yet)
 	// ends-free alignment (mwf_gpu_batch_align_ends; kernel: mwf_ends.hip).  One allocation, made by the first such align and freed with the batch:
-	// [range: n x 4 int32 | info: n x 4 int32 | sub_t_off, sub_q_off: n int64 each | sub_tl, sub_ql: n int32 each | order: n int32, longest pair first]
+	// [range: n x 4 int32 | info: n x 4 int32 | sub_t_off, sub_q_off: n int64 each | sub_tl, sub_ql: n int32 each | order: n int32, longest pair first | the per-pair arrays below]
 	bool ends_last = false;            // the batch's last align was ends-free or an extension: h_kind is 3 for every pair, ranges exist, maps do not
 	bool ext_last = false;             // ... an extension (mwf_gpu_batch_align_ext): the kernel's EXT form, info exists
 	mwf_ends_t ends{};                 // its allowances (finalize()'s re-runs use them)
@@ -258,6 +258,12 @@ struct mwf_gpu_batch_s {
 	DevBuf ends_buf;
 	int32_t *d_range = nullptr, *d_ext_info = nullptr, *d_sub_tl = nullptr, *d_sub_ql = nullptr, *d_ends_order = nullptr;
 	int64_t *d_sub_t_off = nullptr, *d_sub_q_off = nullptr;
+	// per-pair allowances and bands (mwf_gpu_batch_align_ends_pp / _ext_band): two more arrays at the end of ends_buf,
+	// [pp_ends: n x 4 int32 | pp_band: n x 2 int32], uploaded by those calls.  The flags say whether the batch's last align read them: finalize()'s re-runs
+	// repeat them, every other align clears them.
+	int32_t *d_pp_ends = nullptr, *d_pp_band = nullptr;
+	bool pp_ends_last = false, band_last = false;
+	std::vector<mwf_band_t> h_band;    // the bands of that align (band_last): what a launch's penalty bound and widest window are sized by
 };
 
 

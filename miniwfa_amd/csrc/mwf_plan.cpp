@@ -4,6 +4,7 @@
 // fit where it ran (finalize; the routes and their rule: mwf_plan_retry.h).  Split from mwf_engine.cpp in round 5 (no behaviour change).
 #include "mwf_engine.h"
 #include "mwf_plan_retry.h"
+#include "mwf_ends_band.h"
 
 namespace mwf {
 namespace host {
@@ -259,11 +260,30 @@ std::shared_mutex g_dev_gate[kMaxDevices];
 // ---- what the launch functions share ------------------------------------------------------------------------------------
 
 // generic and ends-free kernel: four waves per pair, eight once the windows are wide (measured on 1250 x 50 kb: 708 ms against 782 ms)
-static int window_block(const GroupInfo &G) { return std::min<int64_t>(G.max_len + 1, 2 * G.max_bound + 3) >= 8192 ? 512 : 256; }
+static int64_t widest_window(const GroupInfo &G) { return std::min<int64_t>(G.max_len + 1, 2 * G.max_bound + 3); }
+static int window_block(int64_t widest) { return widest >= 8192 ? 512 : 256; }
+static int window_block(const GroupInfo &G) { return window_block(widest_window(G)); }
 // row stride: whole 256-column chunks plus room for the band kernel's neighbour loads past the last chunk; a good-bit word per 64 columns
 static void set_row_stride(SlotSizes &ws, int64_t max_len) { ws.W = (int32_t)((max_len + 3 + 255) / 256 * 256 + 512), ws.GW = ws.W / 64 + 2; }
 // traceback bytes of a pair at worst: every penalty as wide as the whole matrix
 static int64_t tb_worst(const GroupInfo &G) { return (G.max_bound + 1) * (G.max_len + 1) + 8 * (G.max_bound + 2); }
+
+// ---- ends-free and extension launches under per-pair bands (mwf_ends_band.h) ----
+// One more pair of an ends-free launch's maxima: its penalty bound — the banded one where the batch's last align has bands (gap(tl) + gap(ql) leaves the
+// band) — and, as the window it is expected to reach, the width of its clamped band.
+static void ends_group_add(const mwf_gpu_batch_t *b, GroupInfo &G, int32_t i, const Penalty &P, int32_t max_s)
+{
+	const int64_t tl = b->h_tl[i], ql = b->h_ql[i];
+	if (!b->band_last) { G.add(tl, ql, penalty_bound(P, max_s, tl, ql, true), 0, 0); return; }
+	const mwf_band_t &B = b->h_band[(size_t)i];
+	G.add(tl, ql, ends_band_penalty_bound(P.x, P.o1, P.e1, P.o2, P.e2, max_s, tl, ql, true), 0, band_clamped(tl, ql, B.d_lo, B.d_hi).width());
+}
+// the widest window of such a launch: the band's width where there is one
+static int64_t ends_widest_window(const mwf_gpu_batch_t *b, const GroupInfo &G)
+{
+	const int64_t w = widest_window(G);
+	return b->band_last ? std::min<int64_t>(w, std::max<int64_t>(G.max_exp_win, 1)) : w;
+}
 
 // The workspace of `grid` slots of a one-workgroup-per-pair launch, sized and allocated: rings, good bits and, in CIGAR mode, traceback arena (a slot holds `worst`
 // bytes, or its share of the budget), row metadata and CIGAR scratch.  The traceback budget is looked up here, and only when the arena has to grow.
@@ -469,12 +489,15 @@ int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *
 	const mwf_opt_t &opt = rq.opt;
 	const Penalty P = make_penalty(opt);
 	Plan pl;
-	pl.kind = 3, pl.cigar = (opt.flag & MWF_F_CIGAR) != 0, pl.block = window_block(rq.group);
+	const int64_t widest = ends_widest_window(b, rq.group);
+	pl.kind = 3, pl.cigar = (opt.flag & MWF_F_CIGAR) != 0, pl.block = window_block(widest); // (without bands: window_block(rq.group))
 	pl.ext = b->ext_last; // (the form follows the batch, not the request: finalize()'s re-runs repeat the align's mode)
 	const int per_cu = cached_occupancy(g, P, pl, 0, false);
 	const int slots = std::max(1, std::min(rq.slots, g->n_cu * std::max(1, per_cu)));
 	pl.grid = std::max(1, std::min<int>(slots, rq.n_items));
-	if (size_slots(g, P, rq.group, pl.grid, pl.cigar, tb_worst(rq.group), false, pl.ws)) return -1;
+	// (under bands no row of the traceback is wider than the widest band)
+	const int64_t worst = b->band_last ? (rq.group.max_bound + 1) * widest + 8 * (rq.group.max_bound + 2) : tb_worst(rq.group);
+	if (size_slots(g, P, rq.group, pl.grid, pl.cigar, worst, false, pl.ws)) return -1;
 	if (getenv("MWF_DEBUG"))
 		fprintf(stderr, "[libmwf_hip] kernel kind 3: block %d, %d workgroup(s) per CU, %d slots, %d pairs; grid %d, traceback %lld B per slot\n", pl.block, per_cu, slots, rq.n_items, pl.grid, (long long)pl.ws.tb_slot_bytes);
 
@@ -488,6 +511,7 @@ int run_ends_kernel(mwf_gpu_t *g, mwf_gpu_batch_t *b, const LaunchReq &rq, int *
 	e.t_beg = b->ends.t_beg, e.t_end = b->ends.t_end, e.q_beg = b->ends.q_beg, e.q_end = b->ends.q_end;
 	e.out_range = b->d_range, e.sub_t_off = b->d_sub_t_off, e.sub_q_off = b->d_sub_q_off, e.sub_tl = b->d_sub_tl, e.sub_ql = b->d_sub_ql;
 	e.ext = pl.ext, e.match = b->ext.match, e.zdrop = b->ext.zdrop, e.out_info = b->d_ext_info;
+	e.pp_ends = b->pp_ends_last ? b->d_pp_ends : nullptr, e.pp_band = b->band_last ? b->d_pp_band : nullptr; // (as the form: what the batch's last align read)
 	if (ran_kind) *ran_kind = 3;
 	return launch_gated(g, b, rq, pl, 0, "kernel launch failed (ends-free)", [&] { return launch_ends(e, pl.grid, pl.block, g->stream); });
 }
@@ -1055,6 +1079,7 @@ static int launch_classes(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt
 static void begin_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t &opt, bool ends_free)
 {
 	b->opt = opt, b->ends_last = ends_free, b->ext_last = false; // (mwf_gpu_batch_align_ext sets ext_last after this)
+	b->pp_ends_last = b->band_last = false;                      // (... and the per-pair calls these: no other align reads the arrays)
 	b->aligned = false, b->finalized = false, b->h_cig_valid = false;
 	b->summary_valid = false, b->map_valid[0] = b->map_valid[1] = false, std::fill(b->text_valid, b->text_valid + MWF_TXT_KINDS, false); // (summaries, maps and text describe the previous align's CIGARs)
 	b->last_grid = 0, b->n_retries = 0, b->dev_retry_used = false;
@@ -1110,9 +1135,17 @@ int mwf_gpu_batch_align(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt)
 // Ends-free alignment (include/miniwfa.h, mwf_ends_t): one launch of mwf_ends.hip's kernel over all pairs, longest first.  No size classes, no whole-device
 // route, no sequence copies; the plan cache of the plain align is left alone, so that a later mwf_gpu_batch_align finds what its last one left.
 // ... and extension alignment (mwf_ext_t) with it: the same launch under the EXT form of the kernel, `ext` non-null.
-static int align_ends_or_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends, const mwf_ext_t *ext)
+// pp_ends: the n pairs' own allowances (`ends` is then its first entry), band: their bands; either may be null.
+static int align_ends_or_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends, const mwf_ext_t *ext, const mwf_ends_t *pp_ends = nullptr,
+                             const mwf_band_t *band = nullptr)
 {
 	if (const char *why = validate(*opt)) { g->err = why; return -2; }
+	if (pp_ends)
+		for (int32_t i = 0; i < b->n; ++i)
+			if (pp_ends[i].t_beg < 0 || pp_ends[i].t_end < 0 || pp_ends[i].q_beg < 0 || pp_ends[i].q_end < 0) {
+				g->err = "ends-free alignment: every allowance (t_beg, t_end, q_beg, q_end) must be >= 0: pair " + std::to_string(i);
+				return -2;
+			}
 	if (ext) {
 		if (ext->match < 1) { g->err = "extension alignment: match must be >= 1"; return -2; }
 		if (ext->zdrop < -1) { g->err = "extension alignment: zdrop must be >= 0, or -1 for no drop rule"; return -2; }
@@ -1127,17 +1160,21 @@ static int align_ends_or_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 	const Penalty P0 = make_penalty(*opt);
 	if (P0.nH > kMaxRing) { g->err = "ends-free alignment: max(x, o1+e1, o2+e2) must be < 256"; return -2; }
 	(void)hipSetDevice(g->device);
-	LaunchReq rq; // every pair, longest first, on as many workgroups as stay resident
-	for (int32_t i = 0; i < b->n; ++i) rq.group.add(b->h_tl[i], b->h_ql[i], penalty_bound(P0, opt->max_s, b->h_tl[i], b->h_ql[i], true), 0, 0);
-	if (rq.group.max_len + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
+	int64_t longest = 0;
+	for (int32_t i = 0; i < b->n; ++i) longest = std::max<int64_t>(longest, (int64_t)b->h_tl[i] + b->h_ql[i]);
+	if (longest + 4 >= ((int64_t)1 << 31)) { g->err = "tl+ql must be below 2^31-4"; return -2; }
 	begin_align(g, b, *opt, true);
 	b->ends = *ends;
 	if (ext) b->ext_last = true, b->ext = *ext;
 	if (b->n == 0) { b->aligned = b->finalized = true; return 0; }
 	const size_t N = (size_t)b->n;
-	if (!b->ends_buf.p) { // [range | info | sub_t_off | sub_q_off | sub_tl | sub_ql | order]
+	b->pp_ends_last = pp_ends != nullptr, b->band_last = band != nullptr;
+	if (band) b->h_band.assign(band, band + N);
+	LaunchReq rq; // every pair, longest first, on as many workgroups as stay resident
+	for (int32_t i = 0; i < b->n; ++i) ends_group_add(b, rq.group, i, P0, opt->max_s);
+	if (!b->ends_buf.p) { // [range | info | sub_t_off | sub_q_off | sub_tl | sub_ql | order | pp_ends | pp_band]
 		const size_t r_bytes = align_up(N * 16, 16), o_bytes = N * 8, l_bytes = align_up(N * 4, 16);
-		if (ensure(g, b->ends_buf, 2 * r_bytes + 2 * o_bytes + 3 * l_bytes)) return -1;
+		if (ensure(g, b->ends_buf, 3 * r_bytes + 3 * o_bytes + 3 * l_bytes)) return -1;
 		char *base = (char*)b->ends_buf.p;
 		b->d_range = (int32_t*)base, base += r_bytes;
 		b->d_ext_info = (int32_t*)base, base += r_bytes;
@@ -1145,9 +1182,14 @@ static int align_ends_or_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *
 		b->d_sub_q_off = (int64_t*)base, base += o_bytes;
 		b->d_sub_tl = (int32_t*)base, base += l_bytes;
 		b->d_sub_ql = (int32_t*)base, base += l_bytes;
-		b->d_ends_order = (int32_t*)base;
+		b->d_ends_order = (int32_t*)base, base += l_bytes;
+		b->d_pp_ends = (int32_t*)base, base += r_bytes;
+		b->d_pp_band = (int32_t*)base;
 		if (upload_segments(g, (char*)b->d_ends_order, std::vector<Seg>{Seg{b->h_len_order.data(), N * 4}})) { release(g, b->ends_buf); return -1; }
 	}
+	// (stream order: a kernel of the batch's previous align that still reads the arrays is through before the copies land)
+	if (pp_ends && upload_segments(g, (char*)b->d_pp_ends, std::vector<Seg>{Seg{pp_ends, N * sizeof(mwf_ends_t)}})) return -1;
+	if (band && upload_segments(g, (char*)b->d_pp_band, std::vector<Seg>{Seg{band, N * sizeof(mwf_band_t)}})) return -1;
 	if (place_results(g, b, (opt->flag & MWF_F_CIGAR) != 0)) return -1;
 	const bool was_busy = b->busy;
 	b->busy = true;
@@ -1172,6 +1214,24 @@ int mwf_gpu_batch_align_ext(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *o
 	if (!g || !b || !opt || !ext) return -1;
 	const mwf_ends_t ends = {0, INT32_MAX, 0, INT32_MAX};
 	return align_ends_or_ext(g, b, opt, &ends, ext);
+}
+
+// Ends-free alignment with the pairs' own allowances and bands (include/miniwfa.h, mwf_band_t): the same launch; the kernel reads the arrays per pair.
+int mwf_gpu_batch_align_ends_pp(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ends_t *ends, int32_t n_ends, const mwf_band_t *band)
+{
+	if (!g || !b || !opt) return -1;
+	if (!ends) { g->err = "ends-free alignment: ends must not be NULL"; return -2; }
+	if (n_ends != 1 && n_ends != b->n) { g->err = "ends-free alignment: n_ends must be 1 or the batch's number of pairs"; return -2; }
+	return align_ends_or_ext(g, b, opt, ends, nullptr, n_ends == 1 ? nullptr : ends, band);
+}
+
+// ... and extension alignment under the pairs' bands
+int mwf_gpu_batch_align_ext_band(mwf_gpu_t *g, mwf_gpu_batch_t *b, const mwf_opt_t *opt, const mwf_ext_t *ext, const mwf_band_t *band)
+{
+	if (!g || !b || !opt || !ext) return -1;
+	if (!band) { g->err = "extension alignment: band must not be NULL"; return -2; }
+	const mwf_ends_t ends = {0, INT32_MAX, 0, INT32_MAX};
+	return align_ends_or_ext(g, b, opt, &ends, ext, nullptr, band);
 }
 
 } // extern "C"
@@ -1307,6 +1367,10 @@ static int run_list(mwf_gpu_t *g, mwf_gpu_batch_t *b, std::vector<int32_t> &ids,
 	rq.opt = b->opt;
 	if (step0) rq.opt.step = 0;
 	const mwf_opt_t &o = rq.opt;
+	if (T.launch == LAUNCH_ENDS) { // (the align's own sizing: under bands the banded bound and the bands' widths)
+		const Penalty P = make_penalty(o);
+		for (int32_t i : ids) ends_group_add(b, rq.group, i, P, o.max_s);
+	} else
 	for (int32_t i : ids) rq.group.add(b->h_tl[i], b->h_ql[i], penalty_bound(o, b->h_tl[i], b->h_ql[i], true), penalty_bound(o, b->h_tl[i], b->h_ql[i], false), 0);
 	const GroupInfo &G = rq.group;
 	DevBuf &tmp = g->retry_ids;
